@@ -10,10 +10,19 @@ GPU, contiguous shards, no collective on the data path -> "scaling": "weak").
     python bench.py [--gpus N] [--steps K] [--warmup W]   (N > 1: starts N ranks itself)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU; N must match)
     python bench.py --config 3|4   (supplementary lines for DESIGN.md)
+    python bench.py --full   (the line with everything else: see below)
+    python bench.py --dump-outputs DIR   (what the last timed step computed, as .npy)
 
 Rank 0 prints one JSON line.  value = Gbit/s of plaintext round-trip goodput
 over all ranks = sum_ranks(payload bytes per step) * 8 * K / max_rank(time of
 K steps).
+
+A plain run sets up, warms up, times the K steps and prints the line with the
+figures those steps give (value, ms_per_step, per-kernel times, HBM fractions).
+--full adds what takes work of its own: the verification of the timed batch
+(statuses, whole-batch round trip, the OpenSSL EVP sample), the sustained steps
+with power and clock sampling (and the roofline figures priced at that clock),
+and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -40,6 +49,13 @@ def parse(argv=None):
     # steady state a loaded gateway runs at)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4))
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the timed batch (statuses, round trip, EVP sample), run the "
+                         "sustained steps with power sampling and the CPU baseline; the options "
+                         "below that tune those legs only matter with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of the packets, at most 64 MB)")
     ap.add_argument("--packets", type=int, default=0,
                     help="config 2: packets per GPU (0 = 1M at 1350 B; other --size values keep the "
                          "same payload bytes per step, 1M x 1350 B, rounded to whole 512-packet groups)")
@@ -73,12 +89,73 @@ def parse(argv=None):
                          "'sustained' (the power-capped steady state; never the headline value)")
     ap.add_argument("--evp-sample", type=int, default=257,
                     help="sealed datagrams compared byte for byte against OpenSSL EVP")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the line is the time of the timed steps)")
+    return args
+
+
+# ---------------------------------------------------------------------------
+# --dump-outputs: the packets whose bytes are written are a seeded sample (the
+# same packets for the same arguments), sized so a dump stays under 64 MB
+# ---------------------------------------------------------------------------
+DUMP_SEED = 0x44554D50  # "DUMP"
+DUMP_PACKET_BYTES = 40_000_000  # float32 bytes of the sampled datagrams + plaintexts
+DUMP_STATUS_BYTES = 16_000_000  # float32 bytes of the two status arrays when written whole
+
+
+def dump_rows(sizes, budget: int = DUMP_PACKET_BYTES):
+    """Sorted indices of the sampled packets: a seeded permutation's longest prefix whose
+    datagrams (P + 32) and plaintexts (P), one float32 per byte, fit in `budget`."""
+    import numpy as np
+    sizes = np.asarray(sizes, np.int64)
+    perm = np.random.default_rng(DUMP_SEED).permutation(len(sizes))
+    cost = np.cumsum(4 * (2 * sizes[perm] + 32))
+    return np.sort(perm[:int(np.searchsorted(cost, budget, side="right"))])
+
+
+def to_host(t):
+    """Device tensor -> numpy, through a pinned buffer (a copy engine write into
+    locked pageable memory is the path DESIGN.md §6 keeps big copies off)."""
+    import torch
+    if not t.is_cuda:
+        return t.numpy()
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t)
+    torch.cuda.synchronize(t.device)
+    return host.numpy().copy()
+
+
+def dump_statuses(rows, **st):
+    """The status arrays whole while both fit in DUMP_STATUS_BYTES, else at `rows`."""
+    import torch
+    n = len(next(iter(st.values())))
+    if 4 * n * len(st) > DUMP_STATUS_BYTES:
+        sel = torch.from_numpy(rows).to(next(iter(st.values())).device)
+        return {f"{k}_sampled": to_host(v[sel].float()) for k, v in st.items()}
+    return {k: to_host(v.float()) for k, v in st.items()}
+
+
+def dump_outputs(wl, outdir: str, rank: int, world: int) -> dict:
+    """Write wl.outputs() (name -> float32 / float64 array) as outdir/<name>.npy; with more
+    than one rank each writes its own shard as <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total, names = 0, []
+    for name, a in wl.outputs().items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        fn = f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(outdir, fn), a)
+        total += a.nbytes
+        names.append(fn)
+    assert total <= 64_000_000, f"--dump-outputs wrote {total} bytes"
+    return {"dir": outdir, "files": names, "bytes": total}
 
 
 # ---------------------------------------------------------------------------
 # workloads: each has .step(stream, evs) (events: before seal, between, after
-# open), .verify() -> bool, .packets, .payload_bytes, .launch_bytes
+# open), .verify() -> bool, .outputs() -> {name: array} (what the last step left,
+# for --dump-outputs), .packets, .payload_bytes, .launch_bytes
 # {seal, open}, .kernels {seal, open} (rocprof names), .describe() -> dict
 # ---------------------------------------------------------------------------
 class StridedWorkload:
@@ -190,6 +267,21 @@ class StridedWorkload:
         ok = int((self.st_seal != 0).sum()) == 0 and int((self.st_open != 0).sum()) == 0
         return ok and torch.equal(self.back.view(n, S)[:, o:o + P], self.pt.view(n, S)[:, 16:16 + P])
 
+    def outputs(self):
+        """What a caller of the timed step holds after it: the sealed datagrams and the
+        opened plaintexts of the sampled packets (one float32 per byte), and the two
+        status arrays.  (--op seal / open: the buffer the op does not write is as the
+        setup left it.)"""
+        import numpy as np
+        import torch
+        n, S, P, o = self.n, self.S, self.P, self.open_off
+        rows = dump_rows(np.full(n, P))
+        sel = torch.from_numpy(rows).to(self.wire.device)
+        return {"sample_rows": rows.astype(np.float64),
+                "datagrams": to_host(self.wire.view(n, S)[sel][:, :P + 32].float()),
+                "plaintexts": to_host(self.back.view(n, S)[sel][:, o:o + P].float()),
+                **dump_statuses(rows, seal_status=self.st_seal, open_status=self.st_open)}
+
     def size_hist(self):
         return {self.P: self.n}
 
@@ -289,6 +381,26 @@ class DescWorkload:
         b = self.b
         ok = int((b.st_seal != 0).sum()) == 0 and int((b.st_open != 0).sum()) == 0
         return ok and b.round_trip_equal()
+
+    def outputs(self):
+        """As StridedWorkload.outputs; the sampled packets differ in size, so their
+        datagrams (and plaintexts) are concatenated in `sample_rows` order."""
+        import numpy as np
+        import torch
+        b = self.b
+        rows = dump_rows(b.sizes)
+        dev = b.wire.device
+
+        def gather(buf, starts, lens):
+            first = np.repeat(starts - np.concatenate(([0], np.cumsum(lens)[:-1])), lens)
+            idx = first + np.arange(int(lens.sum()), dtype=np.int64)
+            return to_host(buf[torch.from_numpy(idx).to(dev)].float())
+
+        P = b.sizes[rows].astype(np.int64)
+        return {"sample_rows": rows.astype(np.float64),
+                "datagrams": gather(b.wire, b.offs[rows], P + 32),
+                "plaintexts": gather(b.out, b.offs[rows] + 16, P),
+                **dump_statuses(rows, seal_status=b.st_seal, open_status=b.st_open)}
 
     def sample(self, k):
         return self.b.sample(k, self.keys, self.key_index)
@@ -647,17 +759,22 @@ def run(args, factory=None, device_fn=None, device_count=None):
         print(json.dumps({"seal_ms": [round(x, 4) for x in seal_ms],
                           "open_ms": [round(x, 4) for x in open_ms]}), file=sys.stderr, flush=True)
 
-    # correctness of what was timed: statuses + round-trip identity (whole batch)
-    # + a sample of sealed datagrams byte for byte against OpenSSL EVP
-    ok = bool(wl.verify())
-    evp = evp_check(wl, args.evp_sample)
-    ok = ok and evp.get("mismatches", 0) == 0
-    if world > 1:
-        f = torch.tensor([0 if ok else 1], dtype=torch.int64)
-        dist.all_reduce(f, op=dist.ReduceOp.MAX)
-        ok = int(f.item()) == 0
+    # what the last timed step left, before anything below runs the kernels again
+    dumped = dump_outputs(wl, args.dump_outputs, rank, world) if args.dump_outputs else None
+
+    # --full: correctness of what was timed: statuses + round-trip identity (whole
+    # batch) + a sample of sealed datagrams byte for byte against OpenSSL EVP
+    ok, evp = True, None
+    if args.full:
+        ok = bool(wl.verify())
+        evp = evp_check(wl, args.evp_sample)
+        ok = ok and evp.get("mismatches", 0) == 0
+        if world > 1:
+            f = torch.tensor([0 if ok else 1], dtype=torch.int64)
+            dist.all_reduce(f, op=dist.ReduceOp.MAX)
+            ok = int(f.item()) == 0
     sustained = None
-    if ok and args.sustain_seconds > 0 and args.steps > 0:
+    if args.full and ok and args.sustain_seconds > 0:
         # the kernels run at the package power limit (profiles/r02_power.json);
         # over the first tens of ms the clock is still settling, so the K-step
         # line above and a seconds-long run can differ by a few %.  Every rank
@@ -776,18 +893,24 @@ def run(args, factory=None, device_fn=None, device_count=None):
             "roundtrip_hbm_frac": round(sum(wl.launch_bytes[k] for k in ran) /
                                         (sum(avg[k] for k in ran) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
             "packets_per_step": int(total_pkts),
-            "verified": "all statuses Ok, open(seal(x)) == x over the whole batch, and "
-                        f"{evp.get('checked', 0)} sealed datagrams spread over the batch equal "
-                        "OpenSSL EVP_chacha20_poly1305 with NepTUN framing",
-            "evp_sample": evp,
-            "sustained": sustained,
+            "full": args.full,
         }
+        if args.full:
+            line.update({
+                "verified": "all statuses Ok, open(seal(x)) == x over the whole batch, and "
+                            f"{evp.get('checked', 0)} sealed datagrams spread over the batch equal "
+                            "OpenSSL EVP_chacha20_poly1305 with NepTUN framing",
+                "evp_sample": evp,
+                "sustained": sustained,
+            })
+        if dumped:
+            line["dumped_outputs"] = dumped
         if world > 1:
             line["per_rank"] = per_rank
         lim = power_limiter(pw)
         if lim:
             line["roofline"]["limiter"] = lim
-        if world == 1 and not args.no_cpu_baseline and args.config == 2:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == 2:
             # (at --size P and --op: the CPU path at the same size, the same operation)
             cpus = host_cpus()
             # one thread per physical core this job may use: the GPU box grants a

@@ -24,7 +24,8 @@ def _worker(rank, world, port, outdir, fail_rank, device_count=None):
     if fail_rank is not None:
         os.environ["FAKE_FAIL_RANK"] = str(fail_rank)
     import bench
-    args = bench.parse(["--gpus", str(world), "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0.05"])
+    args = bench.parse(["--gpus", str(world), "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline",
+                        "--sustain-seconds", "0.05"])
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         rc = bench.run(args, factory=FakeWorkload, device_fn=cpu_device,
@@ -144,7 +145,7 @@ def _bench_cli(args, extra_env=None, timeout=120):
     return out.returncode, [x for x in out.stdout.splitlines() if x.startswith("{")]
 
 
-COMMON = ["--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0.05"]
+COMMON = ["--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline", "--sustain-seconds", "0.05"]
 
 
 def test_gpus_flag_starts_that_many_ranks():
@@ -205,3 +206,64 @@ def test_gpus_flag_two_ranks_on_the_gpu(torch_cuda):
     assert line["n_gpus"] == 2 and len(line["per_rank"]) == 2
     assert line["packets_per_step"] == 2 * 65536
     assert "error" not in line and line.get("verified")
+
+
+PLAIN = ["--gpus", "1", "--steps", "7", "--warmup", "1"]
+
+
+def test_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    """Without --full the line carries the figures of the timed steps only: no
+    verification, no sustained steps, no CPU baseline -- and the workload is not
+    asked to verify."""
+    mark = tmp_path / "verified"
+    rc, lines = _bench_cli(PLAIN, extra_env={"FAKE_VERIFY_MARK": str(mark), "FAKE_FAIL_RANK": "0"})
+    assert rc == 0 and len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 7 and line["full"] is False
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "kernel_ms"):
+        assert k in line
+    # rank 0 of the stand-in sleeps 1.5 ms per step
+    assert 1.5 <= line["ms_per_step"] < 50
+    assert line["value"] == pytest.approx(1350 * 1000 * 8 / (line["ms_per_step"] * 1e-3) / 1e9, rel=1e-2)
+    for k in ("verified", "evp_sample", "sustained", "cpu_baseline"):
+        assert k not in line
+    assert not mark.exists()
+    rc, lines = _bench_cli([*PLAIN, "--full", "--no-cpu-baseline", "--sustain-seconds", "0.05"],
+                           extra_env={"FAKE_VERIFY_MARK": str(mark)})
+    assert rc == 0 and mark.exists()
+    line = json.loads(lines[0])
+    assert line["full"] is True and line["verified"] and line["sustained"]["steps"] >= 1
+
+
+def test_dump_outputs_writes_what_the_workload_holds(tmp_path):
+    """--dump-outputs DIR: every array of workload.outputs() as DIR/<name>.npy, float32
+    or float64, listed in the line; two runs with the same arguments write the same."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        rc, lines = _bench_cli([*PLAIN, "--dump-outputs", str(d)])
+        assert rc == 0 and len(lines) == 1
+        line = json.loads(lines[0])
+        assert sorted(line["dumped_outputs"]["files"]) == ["datagrams.npy", "seal_status.npy"]
+        assert sorted(os.listdir(d)) == ["datagrams.npy", "seal_status.npy"]
+    a = np.load(dirs[0] / "datagrams.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, np.arange(12, dtype=np.float32).reshape(3, 4))
+    assert line["dumped_outputs"]["bytes"] == a.nbytes + 4 * 1000
+    for f in ("datagrams.npy", "seal_status.npy"):
+        assert np.array_equal(np.load(dirs[0] / f), np.load(dirs[1] / f))
+
+
+def test_dump_rows_is_a_fixed_sample_within_the_budget():
+    import bench
+    import numpy as np
+    sizes = np.full(1 << 20, 1350)
+    rows = bench.dump_rows(sizes)
+    assert np.array_equal(rows, bench.dump_rows(sizes)) and np.all(np.diff(rows) > 0)
+    assert 0 < 4 * len(rows) * (2 * 1350 + 32) <= bench.DUMP_PACKET_BYTES
+    assert rows[-1] > (1 << 19)  # spread over the batch, not its head
+    assert bench.DUMP_PACKET_BYTES + bench.DUMP_STATUS_BYTES + 8 * len(rows) <= 64_000_000
+    # a batch that fits is written whole; mixed sizes are priced per packet
+    assert np.array_equal(bench.dump_rows(np.full(100, 1350)), np.arange(100))
+    mixed = np.tile(np.array([64, 8900]), 1 << 16)
+    r = bench.dump_rows(mixed)
+    assert 4 * (2 * mixed[r] + 32).sum() <= bench.DUMP_PACKET_BYTES

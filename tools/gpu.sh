@@ -6,7 +6,7 @@
 #   tests            the whole GPU suite (pytest -m gpu)
 #   test=FILE[,..]   the named test files only (tests/FILE)
 #   smoke            __graft_entry__.smoke()
-#   bench[=CFG]      bench.py (default config 2) -> bench_CFG.json
+#   bench[=CFG]      bench.py --full (default config 2) -> bench_CFG.json
 #   trace            rocprofv3 kernel trace + stats of bench.py -> trace/
 #   pmc              tools/pmc_traffic.py (HBM bytes per launch, separate --pmc passes)
 #   valu             tools/pmc_valu.py
@@ -66,11 +66,11 @@ for step in "$@"; do
       for f in $(echo "${step#test=}" | tr ',' ' '); do files="$files tests/$f"; done
       run 600 "$OUT/pytest_$(echo "${step#test=}" | tr ',/' '__').txt" $PYT $files ;;
     smoke) run 180 "$OUT/smoke.txt" python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 400 "$OUT/bench_2.json" python bench.py ;;
-    bench=*) run 600 "$OUT/bench_${step#bench=}.json" python bench.py --config "${step#bench=}" ;;
+    bench) run 400 "$OUT/bench_2.json" python bench.py --full ;;
+    bench=*) run 600 "$OUT/bench_${step#bench=}.json" python bench.py --full --config "${step#bench=}" ;;
     trace)
       run 400 "$OUT/trace_bench.json" rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run \
-        --output-format csv -- python3 bench.py --no-cpu-baseline ;;
+        --output-format csv -- python3 bench.py --full --no-cpu-baseline ;;
     pmc) run 900 "$OUT/pmc.log" python tools/pmc_traffic.py "$OUT/pmc_traffic.json" ;;
     valu) run 600 "$OUT/valu.log" python tools/pmc_valu.py "$OUT/pmc_valu.json" ;;
     xlane) run 300 "$OUT/xlane.jsonl" python tools/bench_xlane.py ${XLANE_ARGS:-} ;;
@@ -138,18 +138,18 @@ for step in "$@"; do
                  "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_INST_LEVEL_VMEM SQ_ACTIVE_INST_VMEM"; do
         i=$((i+1))
         run 300 "$OUT/pmc_p$i.log" rocprofv3 --pmc $grp --output-format csv -d "$OUT/pmc_p$i" -o pmc -- \
-          ${PMC_CMD:?PMC_CMD: the program, e.g. python3 bench.py --no-cpu-baseline}
+          ${PMC_CMD:?PMC_CMD: the program, e.g. python3 bench.py}
       done ;;
     profile)
       python3 -c "import bench, json; print(json.dumps(bench.host_cpus()))" > "$OUT/host_cpus.json"
       for c in ${PROFILE_CONFIGS:-2 3 4}; do
-        run 300 "$OUT/bench_config$c.json" python3 bench.py --config "$c" --steps 20 --warmup 5
+        run 300 "$OUT/bench_config$c.json" python3 bench.py --full --config "$c" --steps 20 --warmup 5
       done
       run 300 "$OUT/trace_bench_config2.json" rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" \
-        -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0
-      run 300 "$OUT/bench_config2_neptun.json" python3 bench.py --layout neptun --steps 20 --warmup 5 --no-cpu-baseline
+        -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --sustain-seconds 0
+      run 300 "$OUT/bench_config2_neptun.json" python3 bench.py --full --layout neptun --steps 20 --warmup 5 --no-cpu-baseline
       run 300 "$OUT/trace_bench_config2_neptun.json" rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/trace_neptun" -o run -- python3 bench.py --layout neptun --steps 20 --warmup 5 --no-cpu-baseline \
+        -d "$OUT/trace_neptun" -o run -- python3 bench.py --full --layout neptun --steps 20 --warmup 5 --no-cpu-baseline \
         --sustain-seconds 0
       run 400 "$OUT/pmc_neptun.log" python3 tools/pmc_traffic.py "$OUT/pmc_traffic_config2_neptun.json" --layout neptun
       for c in ${PROFILE_CONFIGS:-2 3 4}; do

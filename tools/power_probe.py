@@ -84,7 +84,7 @@ def main():
         cmd = sys.argv[sys.argv.index("--") + 1:]
     else:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "20",
-               "--no-cpu-baseline", "--evp-sample", "0"]
+               "--full", "--no-cpu-baseline", "--evp-sample", "0"]
     child = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True)
     samples = []
     t0 = time.time()
