@@ -60,9 +60,6 @@ int wg_launch_desc_hinted(wg_gpu_ctx *ctx, bool seal, const wg_packet_desc *desc
 void wg_ctx_reg_snapshot(wg_gpu_ctx *ctx, std::vector<uint64_t> &out);  // wg_gpu.cpp
 int wg_ctx_claim_slots(wg_gpu_ctx *ctx, uint32_t first, uint32_t count);  // wg_gpu.cpp
 void wg_ctx_release_slots(wg_gpu_ctx *ctx, uint32_t first);              // wg_gpu.cpp
-uint64_t wg_ctx_key_gen(const wg_gpu_ctx *ctx);                          // wg_gpu.cpp
-const uint8_t *wg_ctx_keys(const wg_gpu_ctx *ctx);                       // wg_gpu.cpp
-const uint32_t *wg_ctx_key_index(const wg_gpu_ctx *ctx);                 // wg_gpu.cpp
 
 // ---------------------------------------------------------------------------
 // replay window: ReceivingKeyCounterValidator, session.rs:40-157
@@ -149,18 +146,152 @@ inline uint64_t ld64(const uint8_t *p) {
 }
 inline uint64_t round128(uint64_t x) { return (x + 127) / 128 * 128; }
 
-// Packet copies into / out of pinned staging with streaming (non-temporal)
-// stores: the bytes are read next by the copy engines or the caller, not by this
-// core, and a streaming store skips the read-for-ownership of the destination
-// line (a third of a cached memcpy's DRAM traffic).  WG_TUNN_NT=0: memcpy.
-// Streaming (non-temporal) stores for the host copies into and out of pinned staging:
-// they pay for batches far larger than the last-level cache and cost at smaller ones
-// (1350-B packets, staged: memcpy 40 vs 66-84 us at 64 packets, 1.7-2.0 vs 2.3 ms at
-// 16,384; streaming stores 150-158 vs 146-147 Gbit/s at 262,144; r05y / r05z).
-// WG_TUNN_NT=1 / 0 forces either; default: streaming from 32,768 packets on.
-bool nt_copies(size_t packets) {
-  const char *e = std::getenv("WG_TUNN_NT");
-  return e ? std::atoi(e) != 0 : packets >= 32768;
+// ---------------------------------------------------------------------------
+// Runtime knobs (environment variables): all of this file's, in two blocks.
+//
+// Per call: read_knobs() takes one snapshot at the top of every public batch call; the
+// call keeps it on the engines it runs on (Engine::kn) and reads plain fields from then
+// on.  A change to the environment takes effect at the next call.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kSets = 4;  // staging sets per engine (at most)
+
+struct Knobs {
+  // WG_TUNN_NT=1 / 0: packet copies into / out of pinned staging with streaming
+  // (non-temporal) stores / with memcpy; unset (-1): streaming from 32,768 packets on.
+  // The bytes are read next by the copy engines or the caller, not by this core, and a
+  // streaming store skips the read-for-ownership of the destination line (a third of a
+  // cached memcpy's DRAM traffic): they pay for batches far larger than the last-level
+  // cache and cost at smaller ones (1350-B packets, staged: memcpy 40 vs 66-84 us at 64
+  // packets, 1.7-2.0 vs 2.3 ms at 16,384; streaming stores 150-158 vs 146-147 Gbit/s at
+  // 262,144; r05y / r05z).
+  int nt = -1;
+  bool nt_copies(size_t packets) const { return nt < 0 ? packets >= 32768 : nt != 0; }
+
+  // WG_TUNN_DMA_OUT, DMA batches' output: "direct" (1) -- the AEAD kernel stores each
+  // packet's output straight into the caller's registered dst; "scatter" (0) -- into HBM
+  // staging, then a scatter kernel copies it out; unset (2) -- direct for the chunks whose
+  // output runs sit on whole 128-byte lines of host memory (seal: the datagram at a line
+  // start; open, whose wire grid starts 16 bytes before the plaintext: dst at 16 past a
+  // line start), scatter for the others.  The kernels store 128-byte runs of 8 packets per
+  // instruction: on whole lines that writes host memory faster than the scatter's
+  // contiguous per-packet stores, across line boundaries slower (DESIGN.md section 4,
+  // profiles/r04al_align.jsonl).
+  int dma_out = 2;
+
+  // WG_TUNN_STRIDED=1: uniform decapsulate chunks through the strided text-grid open (off:
+  // into line-aligned slots it wrote host memory slower than the descriptor kernels +
+  // scatter, 255-261 vs 267-273 Gbit/s, profiles/r04st_*)
+  bool strided = false;
+
+  // WG_TUNN_SCATTER_BLOCKS: the DMA batches' scatter grid cap (0: one block per 4 jobs)
+  uint32_t scatter_blocks = 0;
+
+  // WG_TUNN_DMA_STREAMS=0: every stage of a DMA batch's chunk on its staging set's stream
+  // (default: a copy, a kernel and an output stream)
+  bool dma_streams = true;
+
+  // WG_TUNN_CHUNK_KB: staging bytes per pipeline chunk (at least 64 KiB)
+  size_t chunk_bytes = size_t(16) << 20;
+
+  // WG_TUNN_SETS (2..kSets; 0: unset): staging sets a pipeline uses.  With n sets the host
+  // unpacks chunk c - (n - 1) right after submitting chunk c, so n - 1 chunks are queued on
+  // the GPU's streams while the host copies.  Unset: 2 in the staged pipeline; a DMA batch
+  // decides by chunk 0's output form (run_dma).
+  uint32_t sets = 0;
+
+  // WG_TUNN_ZEROCOPY=0 switches to explicit copies.  Zero-copy: the AEAD kernel reads the
+  // pinned input staging and writes the pinned output staging directly over PCIe, so reads
+  // and writes of a chunk share the link in both directions at once instead of running as
+  // H2D copy -> kernel -> D2H copy (measured: 143 / 156 vs 124 / 112 Gbit/s encap / decap,
+  // profiles/r01_tunn_*).
+  bool zero_copy = true;
+
+  // WG_TUNN_DMA=0 turns the DMA runs off.  DMA runs (explicit-copy mode, registered caller
+  // memory): packets whose host buffers sit at a constant pitch with one length, and whose
+  // staging slots do too, move as ONE 2D copy (rows = packets) on the copy engines -- the
+  // way the pinned pipe reaches the link rate (wg_pipe.cpp) -- instead of a host memcpy
+  // into pinned staging.
+  bool dma = true;
+
+  // WG_TUNN_DMA_MIN: registered batches below this many packets take the zero-copy kernels
+  // on the caller's memory instead of a DMA batch: the copy engine's per-batch setup and
+  // completion cost more than the kernel's PCIe reads of a few MB (64 packets encapsulate
+  // 25 vs 37 us, decapsulate 34 vs 43; 4096: 346-385 vs 346-384 and 384-446 vs 445-476;
+  // equal at 16,384; profiles/r05q_small_reg.jsonl, r05ab_tunn_small_reg.jsonl).
+  size_t dma_min = 8192;
+
+  // WG_TUNN_DIRECT_OUT=0: registered decapsulate below dma_min opens into staging and
+  // copies out (default: the zero-copy open writes landing plaintexts straight into the
+  // registered dsts)
+  bool direct_out = true;
+
+  // WG_TUNN_FLAG: zero-copy chunks of at most this many packets learn that their kernel is
+  // done from the kernel's own completion word (0: never) -- a host spin: 6 us from launch
+  // for an empty kernel against 12 us through hipEventSynchronize
+  // (profiles/r05am_launch_latency.json).  Larger grids lose by it: every workgroup's
+  // system-scope release writes back its L2 (4096 packets staged 518 against 389 us,
+  // profiles/r05ao).  A word that has not come after 200 us (a slow or failed launch) hands
+  // over to the event or the stream (wait_chunk), so errors surface.
+  size_t flag_max = 128;
+
+  // WG_TUNN_WORD_EVENT=1: record the chunk's event behind a word-completed kernel too
+  bool word_event = false;
+
+  // WG_TUNN_FAIL_CHUNK=c, test-only fault injection: the batch fails with a HIP error
+  // right after chunk c has been enqueued
+  size_t fail_chunk = ~size_t(0);
+};
+
+// (the only place that reads the per-call knobs' environment)
+Knobs read_knobs() {
+  Knobs k;
+  const char *e;
+  if ((e = std::getenv("WG_TUNN_NT"))) k.nt = std::atoi(e) != 0;
+  if ((e = std::getenv("WG_TUNN_DMA_OUT")))
+    k.dma_out = std::strcmp(e, "scatter") == 0 ? 0 : std::strcmp(e, "direct") == 0 ? 1 : 2;
+  if ((e = std::getenv("WG_TUNN_STRIDED"))) k.strided = std::atoi(e) != 0;
+  if ((e = std::getenv("WG_TUNN_SCATTER_BLOCKS"))) k.scatter_blocks = (uint32_t)std::max(0, std::atoi(e));
+  if ((e = std::getenv("WG_TUNN_DMA_STREAMS"))) k.dma_streams = std::atoi(e) != 0;
+  if ((e = std::getenv("WG_TUNN_CHUNK_KB"))) k.chunk_bytes = std::max<size_t>(64, (size_t)std::atol(e)) << 10;
+  if ((e = std::getenv("WG_TUNN_SETS"))) k.sets = (uint32_t)std::min<int>(kSets, std::max(2, std::atoi(e)));
+  if ((e = std::getenv("WG_TUNN_ZEROCOPY"))) k.zero_copy = std::atoi(e) != 0;
+  if ((e = std::getenv("WG_TUNN_DMA"))) k.dma = std::atoi(e) != 0;
+  if ((e = std::getenv("WG_TUNN_DMA_MIN"))) k.dma_min = (size_t)std::max(0L, std::atol(e));
+  if ((e = std::getenv("WG_TUNN_DIRECT_OUT"))) k.direct_out = std::atoi(e) != 0;
+  if ((e = std::getenv("WG_TUNN_FLAG"))) k.flag_max = (size_t)std::max(0L, std::atol(e));
+  if ((e = std::getenv("WG_TUNN_WORD_EVENT"))) k.word_event = std::atoi(e) != 0;
+  if ((e = std::getenv("WG_TUNN_FAIL_CHUNK"))) k.fail_chunk = (size_t)std::atol(e);
+  return k;
+}
+
+// Read when an engine, a lane or a pool is made, or once per process (the grains).
+size_t env_count(const char *name, size_t dflt) {
+  const char *e = std::getenv(name);
+  return e ? (size_t)std::max(1L, std::atol(e)) : dflt;
+}
+// WG_TUNN_THREADS: copy threads per engine incl. its driver (0: unset, pool_workers
+// sizes the pool from the CPUs this process may run on)
+unsigned threads_knob() {
+  const char *e = std::getenv("WG_TUNN_THREADS");
+  return e ? (unsigned)std::max(1, std::atoi(e)) : 0u;
+}
+// WG_ENGINE_LANES (1..64, default 8): lanes of a shared engine
+uint32_t engine_max_lanes() {
+  const char *e = std::getenv("WG_ENGINE_LANES");
+  return e ? (uint32_t)std::min(64, std::max(1, std::atoi(e))) : 8u;
+}
+// GPU_MAX_HW_QUEUES (the HIP runtime's own, default 4): the hardware queues a process's
+// streams are spread over (make_engine's stream order)
+unsigned hw_queues() {
+  const char *e = std::getenv("GPU_MAX_HW_QUEUES");
+  return e && std::atoi(e) > 0 ? (unsigned)std::atoi(e) : 4u;
+}
+// WG_TUNN_SPIN_US (default 20): pool workers spin this long for the next job before they
+// block on the condition variable: a batch call runs several pool steps back to back,
+// and a blocked worker's wake-up costs tens of microseconds on a loaded host.
+int64_t pool_spin_ns() {
+  const char *e = std::getenv("WG_TUNN_SPIN_US");
+  return (e ? std::max(0, std::atoi(e)) : 20) * 1000ll;
 }
 // The fewest packets worth a pool part of their own.  A blocked worker wakes tens of
 // microseconds late on a loaded host (workers block 20 us after their last part, and a
@@ -170,10 +301,6 @@ bool nt_copies(size_t packets) {
 // into parts of WG_TUNN_GRAIN_COPY (64) packets once a batch has WG_TUNN_COPY_SPLIT
 // (512) packets, and run on the caller below that (profiles/r05ai_*: 2-part copies were
 // the slowest form, 256 packets copy faster alone, 512+ faster on every worker).
-size_t env_count(const char *name, size_t dflt) {
-  const char *e = std::getenv(name);
-  return e ? (size_t)std::max(1L, std::atol(e)) : dflt;
-}
 size_t grain_light() {
   static const size_t g = env_count("WG_TUNN_GRAIN_LIGHT", 1024);
   return g;
@@ -182,6 +309,8 @@ size_t grain_copy(size_t n) {
   static const size_t g = env_count("WG_TUNN_GRAIN_COPY", 64), split = env_count("WG_TUNN_COPY_SPLIT", 512);
   return n < split ? std::max<size_t>(n, 1) : g;
 }
+
+// packet copy into / out of pinned staging; nt: with streaming stores (Knobs::nt)
 void copy_bytes(uint8_t *dst, const uint8_t *src, size_t n, bool nt) {
   if (!nt || n < 256) {
     std::memcpy(dst, src, n);
@@ -210,22 +339,6 @@ void copy_bytes(uint8_t *dst, const uint8_t *src, size_t n, bool nt) {
   _mm_sfence();  // streaming stores are weakly ordered: visible before the DMA / caller reads
 }
 
-// DMA batches' output (WG_TUNN_DMA_OUT, read per call): "direct" -- the AEAD kernel
-// stores each packet's output straight into the caller's registered dst; "scatter" --
-// into HBM staging, then a scatter kernel copies it out; unset -- direct for the chunks
-// whose output runs sit on whole 128-byte lines of host memory (seal: the datagram at a
-// line start; open, whose wire grid starts 16 bytes before the plaintext: dst at 16 past
-// a line start), scatter for the others.  The kernels store 128-byte runs of 8 packets
-// per instruction: on whole lines that writes host memory faster than the scatter's
-// contiguous per-packet stores, across line boundaries slower (DESIGN.md section 4,
-// profiles/r04al_align.jsonl).  Returns 0 scatter, 1 direct, 2 auto.
-int dma_out_mode() {
-  const char *e = std::getenv("WG_TUNN_DMA_OUT");
-  if (e && std::strcmp(e, "scatter") == 0) return 0;
-  if (e && std::strcmp(e, "direct") == 0) return 1;
-  return 2;
-}
-
 // The chunk's output base for direct output: the lowest of the n device addresses
 // addr(j) (each with its extent ext(j)), or 0 when direct output cannot take the chunk
 // -- an address not 16-byte aligned (the descriptor kernels' alignment rule), with
@@ -242,49 +355,6 @@ uint64_t direct_base(size_t n, Addr addr, Ext ext, int line = -1) {
     hi = std::max(hi, a + ext(j));
   }
   return n && hi - lo < (1ull << 43) ? lo : 0;
-}
-
-// Uniform decapsulate chunks through the strided text-grid open (WG_TUNN_STRIDED=1; off:
-// into line-aligned slots it wrote host memory slower than the descriptor kernels +
-// scatter, 255-261 vs 267-273 Gbit/s, profiles/r04st_*), read per call
-bool dma_strided() {
-  const char *e = std::getenv("WG_TUNN_STRIDED");
-  return e && std::atoi(e) != 0;
-}
-
-// the DMA batches' scatter grid cap (WG_TUNN_SCATTER_BLOCKS, default 0: one block per 4
-// jobs), read per call
-uint32_t scatter_blocks() {
-  const char *e = std::getenv("WG_TUNN_SCATTER_BLOCKS");
-  return e ? (uint32_t)std::max(0, std::atoi(e)) : 0u;
-}
-
-// DMA batches on a copy, a kernel and an output stream (WG_TUNN_DMA_STREAMS=0: every
-// stage of a chunk on its staging set's stream), read per call
-bool dma_streams() {
-  const char *e = std::getenv("WG_TUNN_DMA_STREAMS");
-  return !e || std::atoi(e) != 0;
-}
-
-// DMA batches' chunk ramp (make_chunks; WG_TUNN_RAMP=1 turns it on: it measured
-// nothing, profiles/r04u_tunn_ramp_ab.jsonl), read per call
-bool dma_ramp() {
-  const char *e = std::getenv("WG_TUNN_RAMP");
-  return e && std::atoi(e) != 0;
-}
-
-size_t chunk_bytes() {  // staging bytes per pipeline chunk (WG_TUNN_CHUNK_KB overrides, per call)
-  const char *e = std::getenv("WG_TUNN_CHUNK_KB");
-  return e ? std::max<size_t>(64, (size_t)std::atol(e)) << 10 : size_t(16) << 20;
-}
-constexpr uint32_t kSets = 4;                     // staging sets per engine (at most)
-// staging sets a pipeline uses (WG_TUNN_SETS overrides, 2..kSets): with n sets the
-// host unpacks chunk c - (n - 1) right after submitting chunk c, so n - 1 chunks
-// are queued on the GPU's streams while the host copies
-uint32_t pipeline_sets() {  // (read per call, like chunk_bytes())
-  const char *e = std::getenv("WG_TUNN_SETS");
-  const int x = e ? std::atoi(e) : 2;
-  return (uint32_t)std::min<int>(kSets, std::max(2, x));
 }
 
 // ---------------------------------------------------------------------------
@@ -359,7 +429,7 @@ void bind_thread_to_node(int node) {
 // step waits behind another lane's.
 class Pool {
  public:
-  Pool(unsigned workers, int node) : spin_ns_(spin_ns()) {
+  Pool(unsigned workers, int node) : spin_ns_(pool_spin_ns()) {
     for (unsigned i = 0; i < workers; ++i)
       th_.emplace_back([this, node] {
         bind_thread_to_node(node);
@@ -426,13 +496,6 @@ class Pool {
     unsigned parts = 0, next = 0;  // (next: under the pool's lock)
     std::atomic<unsigned> left{0};
   };
-  // Workers spin this long for the next job before they block on the condition variable
-  // (WG_TUNN_SPIN_US, default 20): a batch call runs several pool steps back to back,
-  // and a blocked worker's wake-up costs tens of microseconds on a loaded host.
-  static int64_t spin_ns() {
-    const char *e = std::getenv("WG_TUNN_SPIN_US");
-    return (e ? std::max(0, std::atoi(e)) : 20) * 1000ll;
-  }
   // (under mu_) the next part of j; a job whose parts are all claimed leaves the list
   unsigned claim(Job *j) {
     const unsigned p = j->next++;
@@ -482,7 +545,7 @@ class Pool {
       seen = agen_.load(std::memory_order_acquire);
     }
   }
-  const int64_t spin_ns_;
+  const int64_t spin_ns_;  // (WG_TUNN_SPIN_US)
   std::vector<std::thread> th_;
   std::mutex mu_;
   std::condition_variable cv_, done_;
@@ -593,25 +656,6 @@ __global__ __launch_bounds__(256) void scatter_kernel(const Scatter *__restrict_
 }
 
 // one pinned + device buffer set of the pipeline
-struct CombSlot {
-  wg_packet_desc *desc = nullptr;  // pinned (host-written; inlined into the launch when small)
-  int32_t *st = nullptr;           // pinned statuses
-  uint32_t *h_flag = nullptr, *d_count = nullptr;
-  uint32_t seq = 0;
-  hipStream_t stream = nullptr;
-  std::atomic<int> readers{0};  // calls of the launch that have not taken their statuses yet
-};
-struct Service;  // (the resident service of the small calls, below)
-struct CombSeg {
-  const wg_packet_desc *descs = nullptr;
-  uint32_t n = 0, max_len = 0;
-  uint64_t in_base = 0, out_base = 0;
-  // the leader's answer
-  std::atomic<int> ready{0};
-  int rc = WG_RC_OK;
-  CombSlot *slot = nullptr;
-  uint32_t off = 0, seq = 0;
-};
 struct Staging {
   uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
   wg_packet_desc *h_desc = nullptr, *d_desc = nullptr;
@@ -638,14 +682,6 @@ struct Staging {
   uint32_t done_seq = 0;
   bool flagged = false;
   bool evented = true;  // `done` was recorded behind the chunk in flight
-  // the chunk in flight went out in a combined launch (Combiner below): its word,
-  // sequence number, statuses and slot are the combiner's
-  CombSeg *comb = nullptr;
-  CombSeg cseg;  // (this set's chunk, when it is posted to a combiner)
-  // the chunk in flight was posted to the engine's resident service (Service below):
-  // its slot and sequence number
-  Service *srv = nullptr;
-  uint32_t srv_slot = 0, srv_seq = 0;
 };
 
 void free_buffers(Staging &s) {
@@ -668,16 +704,6 @@ void free_buffers(Staging &s) {
   s.bytes = s.descs = 0;
 }
 
-// (WG_TUNN_STAGE_NC=1: packet staging as non-coherent pinned memory -- the kernels'
-// zero-copy reads then fill whole L2 lines; an A/B of the small-call cap)
-unsigned stage_data_flags(unsigned fl) {
-  static const bool nc = [] {
-    const char *e = std::getenv("WG_TUNN_STAGE_NC");
-    return e && std::atoi(e) != 0;
-  }();
-  return nc ? (fl | hipHostMallocNonCoherent) : fl;
-}
-
 hipError_t reserve(Staging &s, size_t bytes, size_t descs) {
   hipError_t e = hipSuccess;
   const unsigned fl = s.host_flags;
@@ -688,8 +714,8 @@ hipError_t reserve(Staging &s, size_t bytes, size_t descs) {
     (void)hipFree(s.d_out);
     s.h_in = s.h_out = s.d_in = s.d_out = nullptr;
     s.bytes = 0;
-    if ((e = hipHostMalloc(&s.h_in, bytes, stage_data_flags(fl))) != hipSuccess) return e;
-    if ((e = hipHostMalloc(&s.h_out, bytes, stage_data_flags(fl))) != hipSuccess) return e;
+    if ((e = hipHostMalloc(&s.h_in, bytes, fl)) != hipSuccess) return e;
+    if ((e = hipHostMalloc(&s.h_out, bytes, fl)) != hipSuccess) return e;
     if ((e = hipMalloc(&s.d_in, bytes)) != hipSuccess) return e;
     if ((e = hipMalloc(&s.d_out, bytes)) != hipSuccess) return e;
     s.bytes = bytes;
@@ -754,7 +780,7 @@ size_t compact(Pool &pool, size_t n, Keep keep, Emit emit) {
 // process may run on (its affinity mask, not the machine: a GPU box grants a job a
 // share of a larger host) split over the engines, at most 16
 unsigned pool_workers(unsigned engines) {
-  if (const char *e = std::getenv("WG_TUNN_THREADS")) return (unsigned)std::max(1, std::atoi(e)) - 1;
+  if (const unsigned t = threads_knob()) return t - 1;
   cpu_set_t set;
   unsigned cpus = std::max(1u, std::thread::hardware_concurrency());
   if (sched_getaffinity(0, sizeof set, &set) == 0) cpus = std::max(1, CPU_COUNT(&set));
@@ -786,7 +812,7 @@ struct Engine {
   Scratch scratch;            // the per-call arrays of the calls that borrow this lane
   wg_tunn *owner = nullptr;   // batch owner of the multi-peer calls on this lane
   Driver *driver = nullptr;   // multi-engine Tunns only (the single engine runs on the caller)
-  wg_engine *grp = nullptr;   // a lane: its shared engine (combined small launches)
+  Knobs kn;                   // this call's knobs (set_knobs)
   size_t k0 = 0, k1 = 0;      // this batch's share of the selected packets
   std::vector<Chunk> chunks;
   std::vector<uint64_t> off;  // staging offset of selected packet k0 + j inside its chunk
@@ -808,9 +834,10 @@ struct Engine {
   std::vector<hipEvent_t> cev;
   // DMA batches' copy and kernel streams (direct output): the input copies of chunk
   // c + 1 run under chunk c's kernel; per-chunk events order a chunk's stages and a
-  // staging set's reuse
+  // staging set's reuse.  (dq[2] carries no work: it keeps a lane at 8 streams, on which
+  // the lanes' spread over the hardware queues rests, make_engine.)
   hipStream_t dq[3] = {nullptr, nullptr, nullptr};
-  std::vector<hipEvent_t> ev_in, ev_k;
+  std::vector<hipEvent_t> ev_in;
   // direct-output chunks (the AEAD kernel writes the caller's registered dst itself):
   // per chunk 1 = direct, 0 = staged + scatter; and a pinned sink for the plaintext of
   // packets whose speculated decision keeps them out of dst (never read back)
@@ -829,8 +856,6 @@ struct Engine {
   std::vector<void *> sink_old;  // outgrown sinks: kernels in flight may still write them
   Staging aux;
 };
-
-struct Combiner;  // (combined small launches, below)
 
 }  // namespace
 
@@ -873,9 +898,6 @@ struct wg_engine {
   // NUMA node), held by one such call at a time
   Driver *driver = nullptr;
   std::mutex driver_mu;
-  Combiner *comb[2] = {nullptr, nullptr};  // [seal]: small launches of concurrent calls
-  std::mutex comb_mu;                             // (making them, and the service)
-  Service *srv = nullptr;                         // resident service of the small calls
 };
 
 namespace {
@@ -1006,46 +1028,20 @@ void append_chunks(Engine &E, SizeFn size, size_t a, size_t b, size_t limit) {
   if (k0 < b) E.chunks.push_back(Chunk{k0, b, bytes});
 }
 
-// cut the engine's selected packets (staging size `size(k)` each) into pipeline chunks;
-// ramp (DMA batches, whose input copies of chunk c + 1 run under chunk c's kernel): the
-// first chunks grow 1/8, 1/4, 1/2 of the limit and the tail is re-cut into halving
-// pieces down to 1/8, so that the copy with no kernel under it at the start and the
-// kernel with no copy under it at the end are short
+// cut the engine's selected packets (staging size `size(k)` each) into pipeline chunks
+// of at most `limit` staging bytes (0: Knobs::chunk_bytes)
 template <class SizeFn>
-void make_chunks(Engine &E, SizeFn size, size_t limit = 0, bool ramp = false) {
-  if (!limit) limit = chunk_bytes();
-  const size_t floor = std::max<size_t>(limit / 8, 1);
-  auto lim = [&](size_t idx) { return ramp && idx < 3 ? std::max(floor, limit >> (3 - idx)) : limit; };
+void make_chunks(Engine &E, SizeFn size, size_t limit = 0) {
+  if (!limit) limit = E.kn.chunk_bytes;
   E.chunks.clear();
   E.off.resize(E.k1 - E.k0);
   size_t k0 = E.k0, bytes = 0;
   for (size_t k = E.k0; k < E.k1; ++k) {
     const uint64_t b = size(k);
-    if (bytes && bytes + b > lim(E.chunks.size())) {
+    if (bytes && bytes + b > limit) {
       E.chunks.push_back(Chunk{k0, k, bytes});
       k0 = k;
       bytes = 0;
-    }
-    E.off[k - E.k0] = bytes;
-    bytes += b;
-  }
-  if (k0 < E.k1) E.chunks.push_back(Chunk{k0, E.k1, bytes});
-  if (!ramp || E.chunks.size() < 4) return;
-  // re-cut the last two chunks: each piece half of what is left, until 1/8 of the limit
-  const size_t a = E.chunks[E.chunks.size() - 2].k0;
-  size_t left = E.chunks[E.chunks.size() - 2].bytes + E.chunks.back().bytes;
-  E.chunks.resize(E.chunks.size() - 2);
-  k0 = a;
-  bytes = 0;
-  size_t target = left > 2 * floor ? left / 2 : left;
-  for (size_t k = a; k < E.k1; ++k) {
-    const uint64_t b = size(k);
-    if (bytes && bytes + b > target) {
-      E.chunks.push_back(Chunk{k0, k, bytes});
-      left -= bytes;
-      k0 = k;
-      bytes = 0;
-      target = left > 2 * floor ? left / 2 : left;
     }
     E.off[k - E.k0] = bytes;
     bytes += b;
@@ -1099,48 +1095,19 @@ int for_engines(wg_tunn *t, const std::function<int(Engine &)> &job) {
   return rc;
 }
 
-// Zero-copy (default; WG_TUNN_ZEROCOPY=0 switches to explicit copies): the AEAD
-// kernel reads the pinned input staging and writes the pinned output staging
-// directly over PCIe, so reads and writes of a chunk share the link in both
-// directions at once instead of running as H2D copy -> kernel -> D2H copy
-// (measured: 143 / 156 vs 124 / 112 Gbit/s encap / decap, profiles/r01_tunn_*).
-bool zero_copy() {  // (read per batch)
-  const char *e = std::getenv("WG_TUNN_ZEROCOPY");
-  return !e || std::atoi(e) != 0;
-}
-
-// direct mode is possible at all: zero-copy kernels and some registered memory
+// direct mode is possible at all: zero-copy kernels (Knobs::zero_copy) and some
+// registered memory
 bool direct_possible(Engine &E) {
-  if (!zero_copy()) return false;
+  if (!E.kn.zero_copy) return false;
   wg_ctx_reg_snapshot(E.ctx, E.reg);
   return !E.reg.empty();
 }
-// this batch moves registered buffers by DMA runs (explicit copies; one engine, or with
+// this batch moves registered buffers by DMA runs (Knobs::dma; one engine, or with
 // multi_ok every engine of a multi-GPU Tunn on its own share)
-bool dma_possible(wg_tunn *t, Engine &E, bool multi_ok = false);
-// DMA runs (explicit-copy mode, registered caller memory): packets whose host
-// buffers sit at a constant pitch with one length, and whose staging slots do
-// too, move as ONE 2D copy (rows = packets) on the copy engines -- the way the
-// pinned pipe reaches the link rate (wg_pipe.cpp) -- instead of a host memcpy
-// into pinned staging.  WG_TUNN_DMA=0 turns it off.
-bool dma_runs() {  // (read per batch, like the other WG_TUNN_* knobs)
-  const char *e = std::getenv("WG_TUNN_DMA");
-  return !e || std::atoi(e) != 0;
-}
-// Registered batches below this many packets take the zero-copy kernels on the caller's
-// memory instead of a DMA batch: the copy engine's per-batch setup and completion cost
-// more than the kernel's PCIe reads of a few MB (WG_TUNN_DMA_MIN, default 8192; 64 packets
-// encapsulate 25 vs 37 us, decapsulate 34 vs 43; 4096: 346-385 vs 346-384 and 384-446 vs
-// 445-476; equal at 16,384; profiles/r05q_small_reg.jsonl, r05ab_tunn_small_reg.jsonl).
-// Registered decapsulate below dma_min(): the zero-copy open writes landing plaintexts
-// straight into the registered dsts (WG_TUNN_DIRECT_OUT=0: into staging, copied out)
-bool direct_out_small() {
-  const char *e = std::getenv("WG_TUNN_DIRECT_OUT");
-  return !e || std::atoi(e) != 0;
-}
-size_t dma_min() {
-  const char *e = std::getenv("WG_TUNN_DMA_MIN");
-  return e ? (size_t)std::max(0L, std::atol(e)) : 8192u;
+bool dma_possible(wg_tunn *t, Engine &E, bool multi_ok = false) {
+  if (!E.kn.dma || (!multi_ok && t->eng.size() != 1)) return false;
+  wg_ctx_reg_snapshot(E.ctx, E.reg);
+  return !E.reg.empty();
 }
 
 // Cut packets [a, b) with use(k) into runs: host(k) pointer, width(k) bytes,
@@ -1192,55 +1159,19 @@ hipError_t copy_runs(const std::vector<Run> &runs, uint8_t *dev_base, bool h2d, 
   }
   return hipSuccess;
 }
-size_t max_runs(size_t m) { return std::max<size_t>(16, m / 16); }  // (16: the ramp's small chunks)
+size_t max_runs(size_t m) { return std::max<size_t>(16, m / 16); }  // (a chunk's input runs, at least 16)
 
-bool dma_possible(wg_tunn *t, Engine &E, bool multi_ok) {
-  if (!dma_runs() || (!multi_ok && t->eng.size() != 1)) return false;
-  wg_ctx_reg_snapshot(E.ctx, E.reg);
-  return !E.reg.empty();
-}
-
-// Test-only fault injection: WG_TUNN_FAIL_CHUNK=c makes the batch fail with a
-// HIP error right after chunk c has been enqueued (read per call).
-int injected_failure(size_t c) {
-  const char *e = std::getenv("WG_TUNN_FAIL_CHUNK");
-  if (e && (size_t)std::atol(e) == c)
+// (Knobs::fail_chunk, test-only: fail right after chunk c has been enqueued)
+int injected_failure(const Engine &E, size_t c) {
+  if (E.kn.fail_chunk == c)
     return wg_pipe_fail(WG_RC_HIP_ERROR, "tunn: injected failure (WG_TUNN_FAIL_CHUNK)", hipSuccess);
   return WG_RC_OK;
 }
 
-// Every exit from run_chunks -- error paths included -- leaves both staging
-// sets idle: work still queued on a set is waited for (its kernel may still be
-// writing the pinned staging a later reserve() would free) and `busy` cleared,
-// so the next batch starts from a clean pipeline.
-// Small zero-copy calls learn that their kernel is done from the kernel's own
-// completion word (a host spin: 6 us from launch for an empty kernel against 12 us
-// through hipEventSynchronize, profiles/r05am_launch_latency.json) -- chunks of at
-// most WG_TUNN_FLAG packets (default 128; 0: never).  Larger grids lose by it: every
-// workgroup's system-scope release writes back its L2 (4096 packets staged 518 against
-// 389 us, profiles/r05ao).  The event stays recorded behind the kernel: a word that has
-// not come after 200 us (a slow or failed launch) hands over to the event, so errors
-// surface.
-bool flag_completion(size_t packets) {
-  const char *e = std::getenv("WG_TUNN_FLAG");
-  return packets <= (e ? (size_t)std::max(0L, std::atol(e)) : 128u);
-}
-// (WG_TUNN_WORD_EVENT=1: record the chunk's event behind a word-completed kernel too)
-bool word_event() {
-  const char *e = std::getenv("WG_TUNN_WORD_EVENT");
-  return e && std::atoi(e) != 0;
-}
-hipError_t comb_wait(Staging &S, uint32_t m);
-hipError_t srv_wait(Staging &S, uint32_t m);
-hipError_t wait_chunk(Staging &S, uint32_t m) {
-  if (S.comb) {
-    S.flagged = false;
-    return comb_wait(S, m);
-  }
-  if (S.srv) {
-    S.flagged = false;
-    return srv_wait(S, m);
-  }
+// Small zero-copy chunks (Knobs::flag_max) learn that their kernel is done from the
+// kernel's own completion word; one that has not come after 200 us hands over to the
+// chunk's event (Knobs::word_event) or its stream.
+hipError_t wait_chunk(Staging &S) {
   if (S.flagged) {
     S.flagged = false;
     const volatile uint32_t *f = S.h_flag;
@@ -1259,572 +1190,15 @@ hipError_t wait_chunk(Staging &S, uint32_t m) {
   return S.evented ? hipEventSynchronize(S.done) : hipStreamSynchronize(S.stream);
 }
 
-// Combined small launches.  NepTUN's workers each hand over at most 50 packets
-// (packet_workers.rs:27) from up to num_cpus::get_physical() threads at once
-// (:113-131).  Each such call is one latency-form launch -- a few microseconds of
-// launch and a kernel bound by PCIe latency, not by its 50 packets -- so concurrent
-// calls on one engine queue their launches behind each other.  A combiner per engine
-// and direction merges them: a call posts its chunk (its descriptors, staging bases)
-// and the first poster becomes the leader, which waits for a free launch slot (at most
-// WG_COMBINE_DEPTH combined launches in flight: calls arriving meanwhile join the
-// next one), takes every posted chunk, writes one descriptor array (absolute
-// addresses) and makes ONE launch with one completion word for all of them; each
-// call then waits for that word, copies its statuses and goes on with its own
-// in-order decisions.  Per packet the kernel does exactly what the call's own launch
-// would have done.  Off by default (WG_COMBINE=1 turns it on): measured at 8 threads
-// x 50 packets it LOST -- 43 vs 53 Gbit/s staged, 38 vs 54 registered
-// (profiles/r06d_tt_*): the calls' time is the kernel's PCIe round trips, which a
-// shared launch does not shorten, and the slot wait (12 us) came on top.
-constexpr uint32_t kCombSlots = 4, kCombMax = 2048, kCombSegMax = 256;
-struct Combiner {
-  std::mutex mu;
-  std::vector<CombSeg *> pending;
-  bool leader = false;
-  CombSlot slot[kCombSlots];
-  uint32_t next = 0;
-  wg_gpu_ctx *ctx = nullptr;
-  bool seal = false;
-  std::atomic<uint32_t> shared_calls{0};  // chunks that went out in a launch with another call's
-};
-
-bool combine_on() {  // (read per call)
-  const char *e = std::getenv("WG_COMBINE");
-  return e && std::atoi(e) != 0;
-}
-uint32_t combine_depth() {  // combined launches in flight per engine and direction (1 .. kCombSlots)
-  const char *e = std::getenv("WG_COMBINE_DEPTH");
-  return e ? (uint32_t)std::min<long>(kCombSlots, std::max(1L, std::atol(e))) : 2u;
-}
-
-void comb_free(Combiner *C) {
-  if (!C) return;
-  for (CombSlot &S : C->slot) {
-    if (S.stream) (void)hipStreamSynchronize(S.stream);
-    (void)hipHostFree(S.desc);
-    (void)hipHostFree(S.st);
-    (void)hipHostFree(S.h_flag);
-    (void)hipFree(S.d_count);
-    if (S.stream) (void)hipStreamDestroy(S.stream);
-  }
-  delete C;
-}
-
-Combiner *comb_get(wg_engine *g, bool seal) {
-  std::lock_guard<std::mutex> lk(g->comb_mu);
-  if (Combiner *C = g->comb[seal ? 1 : 0]) return C;
-  Combiner *C = new (std::nothrow) Combiner;
-  if (!C) return nullptr;
-  C->ctx = g->ctx;
-  C->seal = seal;
-  DevGuard dg(g->device);
-  bool ok = true;
-  for (CombSlot &S : C->slot) {
-    ok = ok && hipHostMalloc((void **)&S.desc, kCombMax * sizeof(wg_packet_desc), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&S.st, kCombMax * 4, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&S.h_flag, 64, hipHostMallocCoherent) == hipSuccess;
-    ok = ok && hipMalloc((void **)&S.d_count, 64) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMemsetAsync(S.d_count, 0, 64, S.stream) == hipSuccess && hipStreamSynchronize(S.stream) == hipSuccess;
-    if (ok) *S.h_flag = 0;
-  }
-  if (!ok) {
-    comb_free(C);
-    return nullptr;
-  }
-  g->comb[seal ? 1 : 0] = C;
-  return C;
-}
-
-// the launch of slot S has completed (its word, or a stream sync after 200 us)
-hipError_t comb_wait_word(const CombSlot &S, uint32_t seq) {
-  const volatile uint32_t *f = S.h_flag;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t i = 1;; ++i) {
-    if ((int32_t)(*f - seq) >= 0) {  // (this launch or a later one of the slot)
-      std::atomic_thread_fence(std::memory_order_acquire);
-      return hipSuccess;
-    }
-    if ((i & 255u) == 0u &&
-        std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > 200)
-      return hipStreamSynchronize(S.stream);
-    _mm_pause();
-  }
-}
-
-// One leader round: a free slot (at most `depth` launches in flight), every posted
-// chunk that fits, one launch.  Called with C.mu held and C.leader set; returns with
-// C.mu held.
-void comb_launch_round(Combiner &C, std::unique_lock<std::mutex> &lk) {
-  const uint32_t depth = combine_depth();
-  CombSlot &S = C.slot[C.next % depth];
-  lk.unlock();
-  // the slot's previous launch done and its statuses taken (calls arriving meanwhile
-  // join this round)
-  (void)comb_wait_word(S, S.seq);
-  while (S.readers.load(std::memory_order_acquire) != 0) _mm_pause();
-  lk.lock();
-  std::vector<CombSeg *> batch;
-  uint32_t n = 0, max_len = 0;
-  size_t k = 0;
-  for (; k < C.pending.size(); ++k) {
-    CombSeg *g = C.pending[k];
-    if (n + g->n > kCombMax && n) break;
-    batch.push_back(g);
-    n += g->n;
-    max_len = std::max(max_len, g->max_len);
-  }
-  C.pending.erase(C.pending.begin(), C.pending.begin() + (long)k);
-  ++C.next;
-  if (batch.size() > 1) C.shared_calls.fetch_add((uint32_t)batch.size(), std::memory_order_relaxed);
-  lk.unlock();
-  uint32_t off = 0;
-  for (CombSeg *g : batch) {
-    for (uint32_t j = 0; j < g->n; ++j) {
-      wg_packet_desc d = g->descs[j];
-      d.src_off += g->in_base;
-      d.dst_off += g->out_base;
-      S.desc[off + j] = d;
-    }
-    g->off = off;
-    off += g->n;
-  }
-  const uint32_t seq = S.seq + 1;
-  S.readers.store((int)batch.size(), std::memory_order_relaxed);
-  bool flagged = false;
-  int rc = wg_launch_desc_hinted(C.ctx, C.seal, S.desc, n, nullptr, nullptr, S.st, S.stream, max_len, true,
-                                 S.d_count, S.h_flag, seq, &flagged, true, true);
-  if (!rc && !flagged) {  // (not the latency form after all: the host publishes the word)
-    const hipError_t e = hipStreamSynchronize(S.stream);
-    if (e != hipSuccess) rc = wg_pipe_fail(WG_RC_HIP_ERROR, "tunn: combined launch", e);
-    else *(volatile uint32_t *)S.h_flag = seq;
-  }
-  if (rc) S.readers.store(0, std::memory_order_relaxed);
-  S.seq = seq;
-  for (CombSeg *g : batch) {
-    g->rc = rc;
-    g->slot = &S;
-    g->seq = seq;
-    g->ready.store(1, std::memory_order_release);
-  }
-  lk.lock();
-}
-
-// post a chunk; returns once it is launched (g->slot / seq / off) or failed (g->rc)
-int comb_submit(Combiner &C, CombSeg &g) {
-  g.ready.store(0, std::memory_order_relaxed);
-  g.rc = WG_RC_OK;
-  std::unique_lock<std::mutex> lk(C.mu);
-  C.pending.push_back(&g);
-  for (;;) {
-    if (!C.leader) {
-      C.leader = true;
-      // lead until this chunk is out (and whatever else is posted by then)
-      while (!g.ready.load(std::memory_order_acquire) && !C.pending.empty()) comb_launch_round(C, lk);
-      C.leader = false;
-      return g.rc;
-    }
-    lk.unlock();
-    for (uint32_t i = 0; !g.ready.load(std::memory_order_acquire); ++i) {
-      _mm_pause();
-      if ((i & 63u) == 63u) {  // the leader may have stepped down with this chunk still posted
-        lk.lock();
-        if (!C.leader && !g.ready.load(std::memory_order_acquire)) break;
-        lk.unlock();
-      }
-    }
-    if (g.ready.load(std::memory_order_acquire)) return g.rc;
-  }
-}
-
-// the combined launch's completion for a chunk: its word, then its statuses
-hipError_t comb_wait(Staging &S, uint32_t m) {
-  CombSeg *g = S.comb;
-  S.comb = nullptr;
-  const hipError_t e = comb_wait_word(*g->slot, g->seq);
-  if (e == hipSuccess) std::memcpy(S.h_st, g->slot->st + g->off, (size_t)m * 4);
-  g->slot->readers.fetch_sub(1, std::memory_order_acq_rel);
-  return e;
-}
-
-// ---------------------------------------------------------------------------
-// Resident service of the small calls (wg_xlane.hip xlane_service_kernel).
-//
-// A launch per small call costs its ~5 us of launch and, with concurrent callers,
-// its turn on the process's hardware queues: 8 threads x 50 packets held each call
-// 25-28 us against 13-15 alone (profiles/r06d_tt).  A resident kernel does not: it
-// polls kSrvSlots request slots in pinned host memory (a probe of the bare mechanism:
-// 3.9 us from post to done, 3.7 M calls/s from 16 threads, other streams' kernels
-// unaffected, profiles/r06l/doorbell_*.jsonl), and a call is a post -- its descriptors
-// with absolute addresses, then the sequence number -- and a spin on the slot's done
-// word.  Per packet the kernel runs xlane_packet exactly as the latency-form launches.
-//
-// Lifetime: the kernel's workgroups leave on *stop or when their lease (kSrvLeaseUs
-// from their start) runs out.  A call posts only while the lease has more than
-// kSrvMarginUs left on the host's clock (the kernel's workgroups started after the
-// launch, so their leases end later); otherwise, or when the context's key table
-// changed since the launch (a resident kernel may hold the old keys in its caches),
-// the first caller to see it waits for the calls in flight, stops the kernel and
-// launches the next.  A watchdog thread per service stops the kernel once no call has
-// been posted for WG_TUNN_SRV_IDLE_US (1000): a resident kernel counts as device work
-// to hipDeviceSynchronize, which therefore waits for the engine to go idle that long.
-// The watchdog and a poster meet Dekker-style (live / inflight, sequentially
-// consistent): a posted call's kernel is never stopped under it.
-// Measured against the launches (profiles/r06n, r06o, r06r, r06s: 50 x 1350 B, 1 and 8
-// threads, staged and registered): no launch, but the same ~12-15 us of PCIe-bound
-// processing per request (device stamps), so 8 callers run 55-60 Gbit/s either way and
-// one caller +0-13 %; meanwhile a resident kernel makes hipDeviceSynchronize and hipFree
-// anywhere in the process wait for the engine's idle stop.  Off by default: WG_TUNN_SRV=1
-// turns it on.
-constexpr int64_t kSrvLeaseUs = 1000000, kSrvMarginUs = 5000;
-int64_t srv_idle_us() {  // (read per watchdog round)
-  const char *e = std::getenv("WG_TUNN_SRV_IDLE_US");
-  return e ? std::max(100L, std::atol(e)) : 1000L;
-}
-int64_t srv_lease_us() {  // (WG_TUNN_SRV_LEASE_US: tests renew it often; read per launch)
-  const char *e = std::getenv("WG_TUNN_SRV_LEASE_US");
-  return e ? std::max(2000L, std::atol(e)) : kSrvLeaseUs;
-}
-
-struct Service {
-  wg_gpu_ctx *ctx = nullptr;
-  int device = 0;
-  wg::SrvSlot *slots = nullptr;  // pinned, coherent
-  uint32_t *stop = nullptr;      // pinned, coherent
-  uint32_t *d_count = nullptr;   // HBM
-  hipStream_t stream = nullptr;
-  std::mutex mu;                 // restarts
-  std::atomic<int> inflight{0};  // posted calls not yet waited for
-  std::atomic<uint32_t> free_mask{(1u << wg::kSrvSlots) - 1u};
-  std::atomic<bool> live{false};
-  std::atomic<int64_t> post_until{0};  // steady-clock us: no post to the running kernel after
-  std::atomic<uint64_t> key_gen{0};
-  uint32_t seq[wg::kSrvSlots] = {};    // (each touched by its slot's holder only)
-  std::atomic<uint64_t> calls{0}, launches{0};
-  std::atomic<int64_t> last_post{0};   // steady-clock us
-  std::thread watch;                   // the idle stop
-  std::atomic<bool> quit{false};
-  // WG_TUNN_SRV_STAMP=path (a diagnostic): per request the device's phase stamps and
-  // the host's post-to-seen time, summed; written to path when the service ends
-  const char *stamp_path = nullptr;
-  std::mutex stamp_mu;
-  double st_sum[10] = {};  // us: seen->acquired, ->packets, ->acked, ->published, device total, host total;
-                           // packet 0: acquired->descriptor, ->staged, ->tag, ->stores issued
-  uint64_t st_n = 0;
-  int64_t post_us[wg::kSrvSlots] = {};
-};
-
-bool srv_on() {  // (read per call; off by default)
-  const char *e = std::getenv("WG_TUNN_SRV");
-  return e && std::atoi(e) != 0;
-}
-int64_t steady_us() {
-  return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
-// every live service is told to stop at exit (host memory only: registered after the
-// HIP runtime's own exit handlers, so it runs before them)
-std::mutex g_srv_mu;
-std::vector<Service *> g_srvs;
-void srv_stamp_dump(Service *V);
-void srv_atexit() {
-  std::lock_guard<std::mutex> lk(g_srv_mu);
-  bool any = false;
-  for (Service *V : g_srvs) {
-    srv_stamp_dump(V);
-    V->st_n = 0;
-  }
-  for (Service *V : g_srvs) {  // (stopped by the watchdog and still draining counts too)
-    __atomic_store_n(V->stop, 1u, __ATOMIC_RELEASE);
-    V->live.store(false);
-    any = true;
-  }
-  // the grids drained before the runtime tears the queues down (the workgroups see
-  // *stop within a poll, ~2 us; bounded at 100 ms)
-  const int64_t t0 = steady_us();
-  while (any && steady_us() - t0 < 100000) {
-    any = false;
-    for (Service *V : g_srvs)
-      if (V->stream && hipStreamQuery(V->stream) == hipErrorNotReady) any = true;
-    if (any) std::this_thread::sleep_for(std::chrono::microseconds(100));
-  }
-}
-
-// stop the kernel and wait (bounded) for its grid to drain; false: it did not
-bool srv_halt(Service &V) {
-  if (!V.stream) return true;
-  __atomic_store_n(V.stop, 1u, __ATOMIC_RELEASE);
-  V.live.store(false, std::memory_order_seq_cst);
-  const int64_t t0 = steady_us();
-  for (;;) {
-    const hipError_t q = hipStreamQuery(V.stream);
-    if (q != hipErrorNotReady) return true;  // (done, or the stream's error)
-    if (steady_us() - t0 > 3 * kSrvLeaseUs) return false;
-    std::this_thread::yield();
-  }
-}
-
-void srv_watch(Service *V) {
-  while (!V->quit.load(std::memory_order_acquire)) {
-    std::this_thread::sleep_for(std::chrono::microseconds(250));
-    const int64_t idle = srv_idle_us();
-    if (!V->live.load(std::memory_order_acquire) || steady_us() - V->last_post.load() < idle) continue;
-    std::lock_guard<std::mutex> lk(V->mu);
-    if (!V->live.load() || steady_us() - V->last_post.load() < idle) continue;
-    V->live.store(false, std::memory_order_seq_cst);
-    if (V->inflight.load(std::memory_order_seq_cst) != 0) {  // (a post got in: keep it)
-      V->live.store(true, std::memory_order_seq_cst);
-      continue;
-    }
-    __atomic_store_n(V->stop, 1u, __ATOMIC_RELEASE);  // (the next post syncs the stream)
-  }
-}
-
-void srv_stamp_dump(Service *V) {
-  if (!V->stamp_path || !V->st_n) return;
-  if (FILE *f = std::fopen(V->stamp_path, "a")) {
-    const double n = (double)V->st_n;
-    std::fprintf(f,
-                 "{\"requests\": %llu, \"us\": {\"seen_to_acquired\": %.2f, \"acquired_to_packets\": %.2f, "
-                 "\"packets_to_acked\": %.2f, \"acked_to_published\": %.2f, \"device_seen_to_published\": %.2f, "
-                 "\"host_post_to_seen_done\": %.2f, \"pkt0_descriptor\": %.2f, \"pkt0_staged\": %.2f, "
-                 "\"pkt0_keystream_mac\": %.2f, \"pkt0_store_issue\": %.2f}}\n",
-                 (unsigned long long)V->st_n, V->st_sum[0] / n, V->st_sum[1] / n, V->st_sum[2] / n, V->st_sum[3] / n,
-                 V->st_sum[4] / n, V->st_sum[5] / n, V->st_sum[6] / n, V->st_sum[7] / n, V->st_sum[8] / n,
-                 V->st_sum[9] / n);
-    std::fclose(f);
-  }
-}
-
-void srv_free(Service *V) {
-  if (!V) return;
-  srv_stamp_dump(V);
-  {
-    std::lock_guard<std::mutex> lk(g_srv_mu);
-    g_srvs.erase(std::remove(g_srvs.begin(), g_srvs.end(), V), g_srvs.end());
-  }
-  V->quit.store(true, std::memory_order_release);
-  if (V->watch.joinable()) V->watch.join();
-  DevGuard dg(V->device);
-  if (!srv_halt(*V)) return;  // (a grid that does not drain keeps its memory: leaked, not freed under it)
-  if (V->stream) (void)hipStreamDestroy(V->stream);
-  (void)hipHostFree(V->slots);
-  (void)hipHostFree(V->stop);
-  (void)hipFree(V->d_count);
-  delete V;
-}
-
-Service *srv_get(wg_engine *g) {
-  std::lock_guard<std::mutex> lk(g->comb_mu);
-  if (g->srv) return g->srv;
-  Service *V = new (std::nothrow) Service;
-  if (!V) return nullptr;
-  V->ctx = g->ctx;
-  V->device = g->device;
-  DevGuard dg(g->device);
-  bool ok = hipHostMalloc((void **)&V->slots, sizeof(wg::SrvSlot) * wg::kSrvSlots, hipHostMallocCoherent) == hipSuccess;
-  ok = ok && hipHostMalloc((void **)&V->stop, 64, hipHostMallocCoherent) == hipSuccess;
-  ok = ok && hipMalloc((void **)&V->d_count, wg::kSrvSlots * 32 * 4) == hipSuccess;
-  ok = ok && hipStreamCreateWithFlags(&V->stream, hipStreamNonBlocking) == hipSuccess;
-  ok = ok && hipMemsetAsync(V->d_count, 0, wg::kSrvSlots * 32 * 4, V->stream) == hipSuccess &&
-       hipStreamSynchronize(V->stream) == hipSuccess;
-  if (!ok) {
-    srv_free(V);
-    return nullptr;
-  }
-  std::memset(V->slots, 0, sizeof(wg::SrvSlot) * wg::kSrvSlots);
-  *V->stop = 0;
-  V->stamp_path = std::getenv("WG_TUNN_SRV_STAMP");
-  {
-    static std::once_flag once;
-    std::call_once(once, [] { std::atexit(srv_atexit); });
-    std::lock_guard<std::mutex> lk2(g_srv_mu);
-    g_srvs.push_back(V);
-  }
-  V->watch = std::thread(srv_watch, V);
-  g->srv = V;
-  return V;
-}
-
-bool srv_stale(const Service &V) {
-  return !V.live.load(std::memory_order_seq_cst) || steady_us() > V.post_until.load(std::memory_order_acquire) ||
-         wg_ctx_key_gen(V.ctx) != V.key_gen.load(std::memory_order_acquire);
-}
-
-}  // namespace
-
-// a context is being destroyed (wg_gpu.cpp): the services reading its key table stop first
-void wg_srv_ctx_closing(wg_gpu_ctx *ctx) {
-  std::lock_guard<std::mutex> lk(g_srv_mu);
-  for (Service *V : g_srvs)
-    if (V->ctx == ctx) {
-      std::lock_guard<std::mutex> lk2(V->mu);
-      DevGuard dg(V->device);
-      (void)srv_halt(*V);
-    }
-}
-
-namespace {
-
-// a fresh kernel (the caller holds no inflight count)
-int srv_restart(Service &V) {
-  std::lock_guard<std::mutex> lk(V.mu);
-  if (!srv_stale(V)) return WG_RC_OK;
-  while (V.inflight.load(std::memory_order_acquire) != 0) _mm_pause();  // (posted calls finish first)
-  DevGuard dg(V.device);
-  // the previous kernel (live, or stopped by the watchdog and still draining) gone
-  __atomic_store_n(V.stop, 1u, __ATOMIC_RELEASE);
-  V.live.store(false, std::memory_order_seq_cst);
-  TUNN_HIP(hipStreamSynchronize(V.stream), "tunn: service stop");
-  // a request left unanswered (a failed wait) is withdrawn: the next kernel starts from
-  // every slot's done word and must not find an old sequence number waiting there
-  for (uint32_t k = 0; k < wg::kSrvSlots; ++k) {
-    const uint32_t done = __atomic_load_n(&V.slots[k].done, __ATOMIC_ACQUIRE);
-    __atomic_store_n(&V.slots[k].seq, done, __ATOMIC_RELEASE);
-    V.seq[k] = done;
-  }
-  __atomic_store_n(V.stop, 0u, __ATOMIC_RELEASE);
-  TUNN_HIP(hipMemsetAsync(V.d_count, 0, wg::kSrvSlots * 32 * 4, V.stream), "tunn: service counters");
-  // (a key update that completes after this read is seen as a new generation next time)
-  const uint64_t gen = wg_ctx_key_gen(V.ctx);
-  const int64_t t_launch = steady_us(), lease = srv_lease_us();
-  wg::SrvParams prm{V.slots, V.stop, V.d_count, wg_ctx_keys(V.ctx), wg_ctx_key_index(V.ctx),
-                    wg_gpu_ctx_key_slots(V.ctx), (uint64_t)lease * 100u, V.stamp_path ? 1u : 0u};
-  hipLaunchKernelGGL(wg::xlane_service_kernel, dim3(wg::kSrvSlots * wg::kSrvGroup), dim3(wg::kXlaneThreads), 0,
-                     V.stream, prm);
-  TUNN_HIP(hipGetLastError(), "tunn: service launch");
-  V.key_gen.store(gen, std::memory_order_release);
-  V.post_until.store(t_launch + lease - std::min(kSrvMarginUs, lease / 4), std::memory_order_release);
-  V.last_post.store(t_launch);  // (the watchdog's idle clock starts now)
-  V.live.store(true, std::memory_order_seq_cst);
-  V.launches.fetch_add(1, std::memory_order_relaxed);
-  return WG_RC_OK;
-}
-
-// lanes per packet for a request, chosen as the latency-form launches choose them
-// (wg_gpu.cpp xlane_group_hinted) within the slot's kSrvLanes lanes and the kernel's
-// G = 64 ... 8; 0: not a service request
-uint32_t srv_group(uint32_t n, uint32_t max_len, bool seal) {
-  if (n * 8u > wg::kSrvLanes) return 0u;
-  const uint32_t P = seal ? max_len : (max_len > WG_DATA_OVERHEAD_SZ ? max_len - WG_DATA_OVERHEAD_SZ : 0u);
-  const uint32_t nb = 1u + (P + 63u) / 64u;  // keystream blocks of the longest packet
-  uint32_t g = 8u;
-  while (g < nb && g < 64u) g *= 2u;
-  uint32_t G = 64u;
-  while (n * G > wg::kSrvLanes) G /= 2u;
-  return std::min(G, g);
-}
-
-// Post chunk S (m packets, its descriptors relative to in / out) to the service.
-// Returns WG_RC_OK (posted: S.srv set), 1 (not taken: no free slot or too large --
-// the caller launches), or an error.
-int srv_post(Service &V, Staging &S, bool seal, uint32_t m, const uint8_t *in, const uint8_t *out) {
-  if (m == 0 || m > wg::kSrvDescs) return 1;
-  const uint32_t G = srv_group(m, max_desc_len(S.h_desc, m), seal);
-  if (!G) return 1;
-  uint32_t fm = V.free_mask.load(std::memory_order_acquire), bit;
-  do {
-    if (!fm) return 1;
-    bit = (uint32_t)__builtin_ctz(fm);
-  } while (!V.free_mask.compare_exchange_weak(fm, fm & ~(1u << bit), std::memory_order_acq_rel));
-  for (;;) {
-    V.inflight.fetch_add(1, std::memory_order_seq_cst);
-    if (!srv_stale(V)) break;
-    V.inflight.fetch_sub(1, std::memory_order_seq_cst);
-    if (const int rc = srv_restart(V)) {
-      V.free_mask.fetch_or(1u << bit, std::memory_order_acq_rel);
-      return rc;
-    }
-  }
-  wg::SrvSlot &sl = V.slots[bit];
-  const uint64_t ib = reinterpret_cast<uint64_t>(in), ob = reinterpret_cast<uint64_t>(out);
-  for (uint32_t j = 0; j < m; ++j) {
-    wg_packet_desc d = S.h_desc[j];
-    d.src_off += ib;
-    d.dst_off += ob;
-    sl.d[j] = d;
-  }
-  sl.op = seal ? 1u : 0u;
-  sl.n = m;
-  sl.G = G;
-  const uint32_t q = ++V.seq[bit];
-  const int64_t tp = steady_us();
-  V.last_post.store(tp, std::memory_order_relaxed);
-  V.post_us[bit] = tp;
-  __atomic_store_n(&sl.seq, q, __ATOMIC_RELEASE);
-  S.srv = &V;
-  S.srv_slot = bit;
-  S.srv_seq = q;
-  V.calls.fetch_add(1, std::memory_order_relaxed);
-  return WG_RC_OK;
-}
-
-// the posted chunk's done word, then its statuses; the slot and the inflight count
-// are given back on every path
-hipError_t srv_wait(Staging &S, uint32_t m) {
-  Service &V = *S.srv;
-  S.srv = nullptr;
-  wg::SrvSlot &sl = V.slots[S.srv_slot];
-  hipError_t e = hipSuccess;
-  const int64_t t0 = steady_us();
-  for (uint32_t i = 1;; ++i) {
-    if (__atomic_load_n(&sl.done, __ATOMIC_ACQUIRE) == S.srv_seq) break;
-    if ((i & 1023u) == 0u) {
-      const int64_t dt = steady_us() - t0;
-      if (dt > 200) {  // (a slow answer: is the kernel still there?)
-        const hipError_t q = hipStreamQuery(V.stream);
-        if (q == hipSuccess) {  // ended without answering (never expected: see the lease)
-          if (__atomic_load_n(&sl.done, __ATOMIC_ACQUIRE) == S.srv_seq) break;
-          e = hipErrorLaunchFailure;
-          break;
-        }
-        if (q != hipErrorNotReady) {
-          e = q;
-          break;
-        }
-        if (dt > 2 * std::max(kSrvLeaseUs, srv_lease_us())) {
-          e = hipErrorLaunchTimeOut;
-          break;
-        }
-      }
-    }
-    _mm_pause();
-  }
-  if (e == hipSuccess) {
-    std::memcpy(S.h_st, sl.st, (size_t)m * 4);
-    if (V.stamp_path) {
-      const double host = (double)(steady_us() - V.post_us[S.srv_slot]);
-      const uint64_t *t = sl.stamp;
-      std::lock_guard<std::mutex> lk(V.stamp_mu);
-      for (int k = 0; k < 4; ++k) V.st_sum[k] += (double)(t[k + 1] - t[k]) / 100.0;
-      V.st_sum[4] += (double)(t[4] - t[0]) / 100.0;
-      V.st_sum[5] += host;
-      V.st_sum[6] += (double)(t[5] - t[1]) / 100.0;
-      for (int k = 0; k < 3; ++k) V.st_sum[7 + k] += (double)(t[6 + k] - t[5 + k]) / 100.0;
-      ++V.st_n;
-    }
-  } else {
-    V.live.store(false, std::memory_order_release);  // (the next post restarts it)
-  }
-  V.inflight.fetch_sub(1, std::memory_order_acq_rel);
-  V.free_mask.fetch_or(1u << S.srv_slot, std::memory_order_acq_rel);
-  return e;
-}
-
+// Every exit from run_chunks -- error paths included -- leaves both staging
+// sets idle: work still queued on a set is waited for (its kernel may still be
+// writing the pinned staging a later reserve() would free) and `busy` cleared,
+// so the next batch starts from a clean pipeline.
 struct PipelineDrain {
   Engine &E;
   explicit PipelineDrain(Engine &e) : E(e) { drain(); }
   ~PipelineDrain() { drain(); }
   void drain() {
-    for (auto &S : E.st)
-      if (S.comb) {  // (an error path left a combined chunk unwaited: its kernel may still use the staging)
-        CombSeg *g = S.comb;
-        S.comb = nullptr;
-        (void)comb_wait_word(*g->slot, g->seq);
-        g->slot->readers.fetch_sub(1, std::memory_order_acq_rel);
-      }
-    for (auto &S : E.st)
-      if (S.srv) (void)srv_wait(S, 0);  // (an error path left a posted chunk unwaited)
     for (auto &S : E.st)
       if (S.busy) {
         (void)hipStreamSynchronize(S.stream);
@@ -1861,14 +1235,15 @@ int run_chunks(Engine &E, bool seal, Pack pack, Unpack unpack, bool abs_src = fa
                bool abs_dst = false, Post post_kernel = Post(), Mid mid = Mid()) {
   PipelineDrain drain_guard(E);
   const size_t nc = E.chunks.size();
-  const size_t sets = pipeline_sets();
+  const Knobs &kn = E.kn;
+  const size_t sets = kn.sets ? kn.sets : 2;
   const bool zc = E.zc;
   E.ph.chunks += nc;
   size_t next_mid = 0, next_unpack = 0;
   auto stage_mid = [&](size_t c) -> int {
     Staging &S = E.st[c % sets];
     const double a = now_us();
-    TUNN_HIP(wait_chunk(S, (uint32_t)(E.chunks[c].k1 - E.chunks[c].k0)), "tunn: chunk wait");
+    TUNN_HIP(wait_chunk(S), "tunn: chunk wait");
     E.ph.wait_us += now_us() - a;
     const int mr = (int)mid(E.chunks[c], S);
     if (mr == -2)
@@ -1934,7 +1309,7 @@ int run_chunks(Engine &E, bool seal, Pack pack, Unpack unpack, bool abs_src = fa
       uint8_t *out = abs_dst ? nullptr : S.h_out;
       if (timed) TUNN_HIP(hipEventRecord(S.ev[1], S.stream), "tunn: event");
       // (the latency form's completion word: the set's own, made on first use)
-      const bool word = !timed && flag_completion(m);
+      const bool word = !timed && m <= kn.flag_max;
       if (word && !S.h_flag) {
         TUNN_HIP(hipHostMalloc((void **)&S.h_flag, 64, hipHostMallocCoherent), "tunn: completion word");
         TUNN_HIP(hipMalloc((void **)&S.d_count, 64), "tunn: completion counter");
@@ -1942,38 +1317,12 @@ int run_chunks(Engine &E, bool seal, Pack pack, Unpack unpack, bool abs_src = fa
         *S.h_flag = 0;
         S.done_seq = 0;
       }
-      // (a call of one chunk only: a caller never holds a slot's statuses while it
-      // leads another round, whose slot may be that one)
-      int posted = 1;  // (the engine's resident service took the chunk: 0)
-      if (word && nc == 1 && E.grp && srv_on()) {
-        if (Service *V = srv_get(E.grp)) {
-          posted = srv_post(*V, S, seal, (uint32_t)m, in, out);
-          if (posted < 0) return posted;
-          if (posted == 0) S.flagged = true;
-        }
-      }
-      if (posted == 0) {
-        // (posted: no launch, no event -- srv_wait)
-      } else if (word && nc == 1 && m <= kCombSegMax && E.grp && combine_on()) {
-        // one launch with the engine's other small calls of this direction (Combiner)
-        Combiner *C = comb_get(E.grp, seal);
-        if (!C) return wg_pipe_fail(WG_RC_OUT_OF_MEMORY, "tunn: combiner", hipSuccess);
-        S.cseg.descs = S.h_desc;
-        S.cseg.n = (uint32_t)m;
-        S.cseg.max_len = max_desc_len(S.h_desc, m);
-        S.cseg.in_base = reinterpret_cast<uint64_t>(in);
-        S.cseg.out_base = reinterpret_cast<uint64_t>(out);
-        if (const int rc = comb_submit(*C, S.cseg)) return rc;
-        S.comb = &S.cseg;
-        S.flagged = true;
-      } else {
-        if (word) ++S.done_seq;
-        // (the kernel reads the packets over PCIe: hint the latency form's choice)
-        const int rc = wg_launch_desc_hinted(E.ctx, seal, S.h_desc, (uint32_t)m, in, out, S.h_st, S.stream,
-                                             max_desc_len(S.h_desc, m), true, word ? S.d_count : nullptr,
-                                             word ? S.h_flag : nullptr, S.done_seq, &S.flagged, true, true);
-        if (rc) return rc;
-      }
+      if (word) ++S.done_seq;
+      // (the kernel reads the packets over PCIe: hint the latency form's choice)
+      const int rc = wg_launch_desc_hinted(E.ctx, seal, S.h_desc, (uint32_t)m, in, out, S.h_st, S.stream,
+                                           max_desc_len(S.h_desc, m), true, word ? S.d_count : nullptr,
+                                           word ? S.h_flag : nullptr, S.done_seq, &S.flagged, true, true);
+      if (rc) return rc;
       if (timed) TUNN_HIP(hipEventRecord(S.ev[2], S.stream), "tunn: event");
     } else {
       if (!S.in_dma)
@@ -1995,13 +1344,13 @@ int run_chunks(Engine &E, bool seal, Pack pack, Unpack unpack, bool abs_src = fa
       if (timed) TUNN_HIP(hipEventRecord(S.ev[3], S.stream), "tunn: event");
     }
     // (a chunk on the completion word needs no event: its fallback syncs the stream)
-    if (!S.flagged || word_event()) TUNN_HIP(hipEventRecord(S.done, S.stream), "tunn: event");
-    S.evented = !S.flagged || word_event();
+    S.evented = !S.flagged || kn.word_event;
+    if (S.evented) TUNN_HIP(hipEventRecord(S.done, S.stream), "tunn: event");
     S.busy = true;
     S.stage = kSubmitted;
     S.timed = timed;
     E.ph.submit_us += now_us() - pb;
-    if (const int rc = injected_failure(c)) return rc;
+    if (const int rc = injected_failure(E, c)) return rc;
     // overlap: with sets - 1 chunks still queued behind this one, decide the
     // oldest and unpack what has landed (see above)
     if (c + 2 >= sets)
@@ -2095,7 +1444,8 @@ int run_dma(Engine &E, bool seal, double t_prep, size_t n_cap, InHost in_host, I
   };
   // staging: the chunks there are, or a full chunk when more may come (the sets are
   // in use by then: they cannot grow)
-  size_t max_bytes = may_grow ? chunk_bytes() : 0, max_m = may_grow ? chunk_bytes() / 128 + 1 : 0;
+  const Knobs &kn = E.kn;
+  size_t max_bytes = may_grow ? kn.chunk_bytes : 0, max_m = may_grow ? kn.chunk_bytes / 128 + 1 : 0;
   for (const Chunk &ch : E.chunks) {
     max_bytes = std::max(max_bytes, ch.bytes);
     max_m = std::max(max_m, ch.k1 - ch.k0);
@@ -2105,19 +1455,17 @@ int run_dma(Engine &E, bool seal, double t_prep, size_t n_cap, InHost in_host, I
   // outgrown direct-output sinks of earlier batches: their kernels have drained
   for (void *p : E.sink_old) (void)hipHostFree(p);
   E.sink_old.clear();
-  const bool split_streams = dma_streams();
-  const uint32_t scatter_cap = scatter_blocks();
-  const bool split_scatter = std::getenv("WG_TUNN_SPLIT_SCATTER") != nullptr;  // (A/B only)
+  const uint32_t scatter_cap = kn.scatter_blocks;
   // Staging sets (WG_TUNN_SETS overrides): decided by chunk 0's output form -- all kSets
   // when it takes the scatter, whose copy, kernel and scatter then overlap the neighbours'
   // (decapsulate into line-aligned slots 263-269 Gbit/s with 2 sets, 278-285 with 4),
   // 2 for direct output, which 4 sets slowed (profiles/r04se_sets.jsonl, r04f8_*).
-  size_t sets = std::getenv("WG_TUNN_SETS") ? pipeline_sets() : 0;
+  size_t sets = kn.sets;
   TUNN_HIP(reserve_batch(E, std::max(n, n_cap)), "tunn: batch arrays");
   // (each set reserved at its first use in the batch: no chunk of this batch holds it yet)
   TUNN_HIP(reserve(E.st[0], max_bytes + 128, max_m), "tunn: staging");
   auto events = [&](size_t count) -> hipError_t {
-    for (auto *v : {&E.cev, &E.ev_in, &E.ev_k})
+    for (auto *v : {&E.cev, &E.ev_in})
       while (v->size() < count) {
         hipEvent_t ev;
         if (const hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming); e != hipSuccess) return e;
@@ -2148,11 +1496,11 @@ int run_dma(Engine &E, bool seal, double t_prep, size_t n_cap, InHost in_host, I
     // stream, so that chunk c + 1's copies run under chunk c's kernel (the two move data
     // in opposite directions).  Staged output: copies, kernel and scatter on the set's
     // stream -- splitting those too (the scatter on a third stream beside the next
-    // chunk's kernel, its grid capped by WG_TUNN_SCATTER_BLOCKS) measured 3-15 % slower
-    // (profiles/r04sc_scatter.jsonl).  WG_TUNN_DMA_STREAMS=0: every stage on the set's
-    // stream.  Either way a set's reuse by chunk c waits for chunk c - sets.
-    const bool split = split_streams && (!scatter || split_scatter);
-    hipStream_t qi = split ? E.dq[0] : S.stream, qk = split ? E.dq[1] : S.stream, qo = split ? E.dq[2] : S.stream;
+    // chunk's kernel) measured 3-15 % slower (profiles/r04sc_scatter.jsonl).
+    // Knobs::dma_streams off: every stage on the set's stream.  Either way a set's reuse
+    // by chunk c waits for chunk c - sets.
+    const bool split = kn.dma_streams && !scatter;
+    hipStream_t qi = split ? E.dq[0] : S.stream, qk = split ? E.dq[1] : S.stream;
     if (c >= sets) TUNN_HIP(hipStreamWaitEvent(qi, E.cev[c - sets], 0), "tunn: set reuse");
     TUNN_HIP(copy_runs(E.chunk_runs[c], S.d_in, true, qi), "tunn: input runs");
     if (split) {
@@ -2171,20 +1519,16 @@ int run_dma(Engine &E, bool seal, double t_prep, size_t n_cap, InHost in_host, I
       rc = wg_launch_desc_hinted(E.ctx, seal, E.b_desc + j0, (uint32_t)m, S.d_in, out_base, E.b_st + j0, qk,
                                  max_desc_len(E.b_desc + j0, m), false, nullptr, nullptr, 0, nullptr, seal);
     if (rc) return rc;
-    if (scatter) {
-      if (split) {
-        TUNN_HIP(hipEventRecord(E.ev_k[c], qk), "tunn: event");
-        TUNN_HIP(hipStreamWaitEvent(qo, E.ev_k[c], 0), "tunn: event wait");
-      }
+    if (scatter) {  // (behind the kernel, on the set's stream)
       const uint32_t blocks = (uint32_t)((m + 3) / 4);
       hipLaunchKernelGGL(scatter_kernel, dim3(scatter_cap ? std::min(blocks, scatter_cap) : blocks), dim3(256), 0,
-                         qo, E.b_jobs + j0, (uint32_t)m, (const uint8_t *)S.d_out, (const uint8_t *)S.d_in);
+                         qk, E.b_jobs + j0, (uint32_t)m, (const uint8_t *)S.d_out, (const uint8_t *)S.d_in);
       TUNN_HIP(hipGetLastError(), "tunn: scatter launch");
     }
-    TUNN_HIP(hipEventRecord(E.cev[c], scatter ? qo : qk), "tunn: event");
+    TUNN_HIP(hipEventRecord(E.cev[c], qk), "tunn: event");
     S.busy = true;
     E.ph.submit_us += now_us() - pb;
-    if (const int rc2 = injected_failure(c)) return rc2;
+    if (const int rc2 = injected_failure(E, c)) return rc2;
     if (c == 0) {  // the rest of the batch (chunk 0 is on the device meanwhile)
       const double a = now_us();
       const size_t had = E.chunks.size(), k_had = E.k1;
@@ -2269,7 +1613,7 @@ uint64_t validate(const uint8_t *pt, uint32_t P, wg_tunn_result &r) {
 //  * one engine: a double-buffered chunk pipeline; each chunk is decided as it
 //    returns while the next runs on the GPU;
 //  * several engines: the selection is cut into rounds of about
-//    engines x chunk_bytes() staging bytes; in each round every engine opens
+//    engines x Knobs::chunk_bytes staging bytes; in each round every engine opens
 //    its share as one chunk (in parallel on its own GPU and NUMA node), then
 //    the caller decides the round's packets in order, then every engine copies
 //    its share out.  Pinned staging per engine stays one chunk whatever the
@@ -2285,7 +1629,8 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
                   uint8_t *const *dst, Decide decide, Finish finish, Speculate speculate, Grow grow,
                   bool partial, size_t n_cap) {
   const bool multi = t->eng.size() > 1;
-  if (partial && (multi || !dma_runs())) {
+  const Knobs &kn = t->eng[0]->kn;  // (every engine of the call holds the same snapshot)
+  if (partial && (multi || !kn.dma)) {
     grow();
     partial = false;
   }
@@ -2302,7 +1647,7 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
     t->sc->out_dma.resize(t->sc->sel.size(), 0);
     t->sc->spec.resize(t->sc->sel.size(), 0);
   };
-  const bool nt = nt_copies(n_cap);
+  const bool nt = kn.nt_copies(n_cap);
   std::atomic<uint64_t> rx{0};
   // what lands in dst from pinned staging (pt: the plaintext there), then finish
   auto copy_out = [&](Engine &E, const Chunk &ch, const uint8_t *h_out, const wg_packet_desc *h_desc) {
@@ -2424,16 +1769,16 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
   };
   auto dma_batch = [&](Engine &E) -> int {
     const double t_prep = now_us();
-    if (!multi_dma && (multi || n_cap < dma_min() || !dma_possible(t, E) || !registered(E, E.k0, E.k1))) {
+    if (!multi_dma && (multi || n_cap < kn.dma_min || !dma_possible(t, E) || !registered(E, E.k0, E.k1))) {
       if (partial) {  // not for a DMA batch after all: the staged path takes the whole selection
         grow_all();
         split(t, size);
       }
       return 1;
     }
-    make_chunks(E, size, 0, dma_ramp());
-    const int out_mode = dma_out_mode();
-    const bool strided_ok = out_mode == 2 && !wg_ctx_slot_padding(E.ctx) && dma_strided();
+    make_chunks(E, size);
+    const int out_mode = kn.dma_out;
+    const bool strided_ok = out_mode == 2 && !wg_ctx_slot_padding(E.ctx) && kn.strided;
     E.chunk_direct.assign(E.chunks.size(), 0);
     E.chunk_strided.assign(E.chunks.size(), Engine::StridedOpen{});
     auto fill = [&](const Chunk &ch, size_t j0, uint8_t *d_out) -> uint8_t * {
@@ -2500,7 +1845,7 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
       grow_all();
       if (t->sc->sel.size() == had) return 1;
       if (!registered(E, had, t->sc->sel.size())) return 2;
-      append_chunks(E, size, had, t->sc->sel.size(), chunk_bytes());
+      append_chunks(E, size, had, t->sc->sel.size(), E.kn.chunk_bytes);
       E.k1 = t->sc->sel.size();
       E.chunk_direct.resize(E.chunks.size(), 0);
       E.chunk_strided.resize(E.chunks.size(), Engine::StridedOpen{});
@@ -2531,7 +1876,7 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
     } else if (r != 1) {
       return r;
     }
-    E.zc = zero_copy();
+    E.zc = E.kn.zero_copy;
     make_chunks(E, size, inline_decide ? 0 : ~size_t(0));
     // direct input (zero-copy): every datagram 16-byte aligned inside registered memory
     bool direct = direct_possible(E);
@@ -2546,7 +1891,7 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
     // its dst and the others' into the pinned sink, as the DMA batches' direct output
     // does; the in-order decisions then only add the tags (and repair what the
     // speculation missed) -- no plaintext copy-out from staging
-    bool dout = direct && inline_decide && direct_out_small();
+    bool dout = direct && inline_decide && kn.direct_out;
     if (dout) {
       E.ddst.resize(E.k1 - E.k0);
       uint32_t pmax = 0;
@@ -2601,7 +1946,7 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
   if (multi) {
     // registered pools on every engine's share: one DMA batch per engine (see multi_dma)
     split(t, size);
-    bool all = dma_runs() && n_cap >= dma_min();
+    bool all = kn.dma && n_cap >= kn.dma_min;
     for (size_t e = 0; all && e < t->eng.size(); ++e) {
       Engine &E = *t->eng[e];
       DevGuard g(E.device);
@@ -2613,7 +1958,7 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
       std::vector<int> verdict(t->eng.size(), 1);
       rc = for_engines(t, [&](Engine &E) -> int {
         const size_t e = std::find(t->eng.begin(), t->eng.end(), &E) - t->eng.begin();
-        E.zc = zero_copy();
+        E.zc = E.kn.zero_copy;
         const int r = dma_batch(E);
         verdict[e] = r;
         return r == 1 ? WG_RC_OK : r;
@@ -2642,9 +1987,9 @@ int open_selected(wg_tunn *t, const uint8_t *const *datagram, const uint32_t *le
   if (!multi) {
     rc = for_engines(t, engine_job);
   } else {
-    // several engines: rounds of about engines x chunk_bytes() staging bytes
+    // several engines: rounds of about engines x Knobs::chunk_bytes staging bytes
     const size_t n = t->sc->sel.size();
-    const uint64_t cap = (uint64_t)chunk_bytes() * t->eng.size();
+    const uint64_t cap = (uint64_t)kn.chunk_bytes * t->eng.size();
     for (size_t a = 0; a < n && !rc;) {
       size_t b = a;
       uint64_t acc = 0;
@@ -2680,7 +2025,6 @@ void destroy_engine(Engine *E) {
     (void)hipHostFree(E->sink);
     for (void *p : E->sink_old) (void)hipHostFree(p);
     for (hipEvent_t ev : E->ev_in) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : E->ev_k) (void)hipEventDestroy(ev);
     (void)hipHostFree(E->b_desc);
     (void)hipHostFree(E->b_st);
     (void)hipHostFree(E->b_jobs);
@@ -2703,16 +2047,12 @@ void destroy_engine(Engine *E) {
 }
 
 // The HIP runtime spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues
-// (default 4) in creation order, and kernels of one hardware queue run one after
+// (hw_queues()) in creation order, and kernels of one hardware queue run one after
 // another.  Every lane makes the same number of streams (a multiple of 4), so without
 // care st[0] -- the stream of every single-chunk call -- of all lanes shares one or two
 // queues: 8 concurrent 50-packet calls then ran on 2 queues, one after another
 // (profiles/r05av trace).  A lane therefore makes its streams in an order rotated by
 // its index, st[0] of lanes 0, 1, 2, 3 ... landing on consecutive queues.
-unsigned hw_queues() {
-  const char *e = std::getenv("GPU_MAX_HW_QUEUES");
-  return e && std::atoi(e) > 0 ? (unsigned)std::atoi(e) : 4u;
-}
 
 // shared: the engine's pool (a lane), else the engine makes its own; rot: the lane's
 // index (stream order, above)
@@ -2763,11 +2103,6 @@ int make_engine(wg_gpu_ctx *ctx, bool multi, unsigned engines, Engine **out, Poo
 // lanes of a shared engine: streams per lane (staging sets + repair + DMA streams)
 constexpr uint32_t kLaneStreams = kSets + 1 + 3;
 
-uint32_t engine_max_lanes() {  // WG_ENGINE_LANES (1..64, default 8), read when an engine is made
-  const char *e = std::getenv("WG_ENGINE_LANES");
-  return e ? (uint32_t)std::min(64, std::max(1, std::atoi(e))) : 8u;
-}
-
 // borrow a lane (made on first need, up to max_lanes; else wait for one)
 int lane_acquire(wg_engine *g, Engine **out) {
   std::unique_lock<std::mutex> lk(g->mu);
@@ -2780,7 +2115,6 @@ int lane_acquire(wg_engine *g, Engine **out) {
     if (g->lanes.size() < g->max_lanes) {
       Engine *E = nullptr;
       if (const int rc = make_engine(g->ctx, false, 1, &E, g->pool, (unsigned)g->lanes.size())) return rc;
-      E->grp = g;
       g->lanes.push_back(E);
       *out = E;
       return WG_RC_OK;
@@ -2836,6 +2170,11 @@ struct Lease {
   }
 };
 
+// this call's knobs, on every engine it runs on (after the Lease: t->eng is the lane)
+void set_knobs(wg_tunn *t, const Knobs &kn) {
+  for (Engine *E : t->eng) E->kn = kn;
+}
+
 // every context's default engine (wg_tunn_create)
 std::mutex g_default_mu;
 std::vector<std::pair<wg_gpu_ctx *, wg_engine *>> g_default;
@@ -2856,10 +2195,7 @@ int engine_make(wg_gpu_ctx *ctx, wg_engine **out) {
 }
 
 void engine_free(wg_engine *g) {
-  srv_free(g->srv);
   for (Engine *E : g->lanes) destroy_engine(E);
-  comb_free(g->comb[0]);
-  comb_free(g->comb[1]);
   delete g->driver;
   delete g->pool;
   delete g;
@@ -2936,15 +2272,6 @@ int wg_engine_get_info(const wg_engine *e, wg_engine_info *out) {
   out->max_lanes = e->max_lanes;
   out->pool_threads = e->pool->size();
   out->streams = out->lanes * kLaneStreams;
-  {
-    std::lock_guard<std::mutex> cl(const_cast<wg_engine *>(e)->comb_mu);
-    for (const Combiner *C : e->comb)
-      if (C) out->combined += C->shared_calls.load(std::memory_order_relaxed);
-    if (const Service *V = e->srv) {
-      out->served = V->calls.load(std::memory_order_relaxed);
-      out->service_launches = V->launches.load(std::memory_order_relaxed);
-    }
-  }
   return WG_RC_OK;
 }
 
@@ -3113,10 +2440,11 @@ int wg_tunn_session_counters(const wg_tunn *t, uint32_t ring_slot, uint64_t *sen
 // n x Tunn::encapsulate.  t: the batch owner (the Tunn of a single-Tunn call, whose
 // lane / engines and per-call arrays the batch runs on; a lane's owner for a
 // multi-peer call).  peer: nullptr (every packet is t's), or packet i's Tunn.
-static int encap_impl(wg_tunn *t, wg_tunn *const *peer, uint32_t n, const uint8_t *const *src,
+static int encap_impl(wg_tunn *t, const Knobs &kn, wg_tunn *const *peer, uint32_t n, const uint8_t *const *src,
                       const uint32_t *src_len, uint8_t *const *dst, const uint32_t *dst_cap,
                       wg_tunn_result *res) {
   PhaseCall pc(t, n);
+  set_knobs(t, kn);
   const bool many = peer != nullptr;
   Session &s = t->sessions[t->current % WG_N_SESSIONS];  // mod.rs:310 (single-Tunn batches)
   const uint32_t slot = t->first_slot + 2 * (uint32_t)(t->current % WG_N_SESSIONS) + 1;
@@ -3167,7 +2495,7 @@ static int encap_impl(wg_tunn *t, wg_tunn *const *peer, uint32_t n, const uint8_
   // a registered DMA batch puts that part's first chunk on the device while pass 1
   // covers the rest; the reservation grows with the selection.
   const uint64_t ctr0 = s.sending_counter;
-  const size_t n0 = n >= 16384 && dma_runs() && t->eng.size() == 1 && !many ? n / 16 : n;
+  const size_t n0 = n >= 16384 && kn.dma && t->eng.size() == 1 && !many ? n / 16 : n;
   pass1(0, n0);
   bool partial = n0 < n;
   auto grow = [&]() {
@@ -3200,9 +2528,9 @@ static int encap_impl(wg_tunn *t, wg_tunn *const *peer, uint32_t n, const uint8_
   pc.checks_done();
   auto size = [&](size_t k) { return round128((uint64_t)src_len[t->sc->sel[k]] + WG_DATA_OVERHEAD_SZ); };
   split(t, size);
-  const bool nt = nt_copies(n);
+  const bool nt = kn.nt_copies(n);
   const int rc = for_engines(t, [&](Engine &E) -> int {
-    E.zc = zero_copy();
+    E.zc = E.kn.zero_copy;
     // registered src and dst (one engine): the DMA batch -- plaintexts in as runs, the
     // datagrams scattered straight into dst, no host copies and no waits between chunks
     const double t_prep = now_us();
@@ -3223,13 +2551,13 @@ static int encap_impl(wg_tunn *t, wg_tunn *const *peer, uint32_t n, const uint8_
     int left = 1;  // run_dma's verdict: 1 nothing done, 2 the packets from E.k1 on are left
     // (encapsulate has no in-order decisions: every engine of a multi-GPU Tunn runs its
     // contiguous share as a DMA batch of its own, the counters reserved before the split)
-    const bool dma_ok = dma_possible(t, E, true) && n >= dma_min();
+    const bool dma_ok = dma_possible(t, E, true) && n >= kn.dma_min;
     if (!dma_ok) grow_all();
     if (dma_ok) {
       const bool all = registered(E.k0, E.k1);
       if (all) {
-        make_chunks(E, size, 0, dma_ramp());
-        const int out_mode = dma_out_mode();
+        make_chunks(E, size);
+        const int out_mode = kn.dma_out;
         auto fill = [&](const Chunk &ch, size_t j0, uint8_t *d_out) -> uint8_t * {
           const size_t m = ch.k1 - ch.k0;
           // direct output: the seal kernel writes each datagram into the caller's dst
@@ -3282,7 +2610,7 @@ static int encap_impl(wg_tunn *t, wg_tunn *const *peer, uint32_t n, const uint8_
           grow();
           if (t->sc->sel.size() == had) return 1;
           if (!registered(had, t->sc->sel.size())) return 2;
-          append_chunks(E, size, had, t->sc->sel.size(), chunk_bytes());
+          append_chunks(E, size, had, t->sc->sel.size(), E.kn.chunk_bytes);
           E.k1 = t->sc->sel.size();
           return 0;
         };
@@ -3364,10 +2692,11 @@ static int encap_impl(wg_tunn *t, wg_tunn *const *peer, uint32_t n, const uint8_
 
 // n x Tunn::decapsulate; t and peer as in encap_impl, peers: the distinct Tunns of a
 // multi-peer batch
-static int decap_impl(wg_tunn *t, wg_tunn *const *peer, const std::vector<wg_tunn *> *peers, uint32_t n,
-                      const uint8_t *const *datagram, const uint32_t *len, uint8_t *const *dst,
+static int decap_impl(wg_tunn *t, const Knobs &kn, wg_tunn *const *peer, const std::vector<wg_tunn *> *peers,
+                      uint32_t n, const uint8_t *const *datagram, const uint32_t *len, uint8_t *const *dst,
                       const uint32_t *dst_cap, wg_tunn_result *res) {
   PhaseCall pc(t, n);
+  set_knobs(t, kn);
   const bool many = peer != nullptr;
   // pass 1 (stateless checks, reference order; on the pool): parse, session, dst
   // size, index -- and each datagram's counter, so the in-order pass never reads
@@ -3426,7 +2755,7 @@ static int decap_impl(wg_tunn *t, wg_tunn *const *peer, const std::vector<wg_tun
   };
   // a large batch checks its first sixteenth first: a registered DMA batch puts that
   // part's first chunk on the device while pass 1 covers the rest (open_selected)
-  const size_t n0 = n >= 16384 && dma_runs() && t->eng.size() == 1 && !many ? n / 16 : n;
+  const size_t n0 = n >= 16384 && kn.dma && t->eng.size() == 1 && !many ? n / 16 : n;
   pass1(0, n0);
   bool grown = n0 == n;
   auto grow = [&]() {
@@ -3497,7 +2826,7 @@ int wg_tunn_encapsulate_batch(wg_tunn *t, uint32_t n, const uint8_t *const *src,
   std::lock_guard<std::mutex> lk(t->mu);
   Lease lease(t);
   if (lease.rc) return lease.rc;
-  return encap_impl(t, nullptr, n, src, src_len, dst, dst_cap, res);
+  return encap_impl(t, read_knobs(), nullptr, n, src, src_len, dst, dst_cap, res);
 }
 
 int wg_tunn_decapsulate_batch(wg_tunn *t, uint32_t n, const uint8_t *const *datagram,
@@ -3509,7 +2838,7 @@ int wg_tunn_decapsulate_batch(wg_tunn *t, uint32_t n, const uint8_t *const *data
   std::lock_guard<std::mutex> lk(t->mu);
   Lease lease(t);
   if (lease.rc) return lease.rc;
-  return decap_impl(t, nullptr, nullptr, n, datagram, len, dst, dst_cap, res);
+  return decap_impl(t, read_knobs(), nullptr, nullptr, n, datagram, len, dst, dst_cap, res);
 }
 
 // A multi-peer call: the distinct Tunns locked in address order, one lane borrowed,
@@ -3541,13 +2870,14 @@ struct MultiCall {
   ~MultiCall() {}  // (the lease below returns the lane; the locks go last)
 };
 
-static int multi_on_engine(bool seal, wg_engine *e, uint32_t n, wg_tunn *const *tunn, const uint8_t *const *in,
-                    const uint32_t *len, uint8_t *const *dst, const uint32_t *dst_cap, wg_tunn_result *res) {
+static int multi_on_engine(bool seal, const Knobs &kn, wg_engine *e, uint32_t n, wg_tunn *const *tunn,
+                           const uint8_t *const *in, const uint32_t *len, uint8_t *const *dst,
+                           const uint32_t *dst_cap, wg_tunn_result *res) {
   MultiCall mc(e, n, tunn);
   if (mc.rc) return mc.rc;
   Lease lease(mc.owner, mc.lane);
-  return seal ? encap_impl(mc.owner, tunn, n, in, len, dst, dst_cap, res)
-              : decap_impl(mc.owner, tunn, &mc.peers, n, in, len, dst, dst_cap, res);
+  return seal ? encap_impl(mc.owner, kn, tunn, n, in, len, dst, dst_cap, res)
+              : decap_impl(mc.owner, kn, tunn, &mc.peers, n, in, len, dst, dst_cap, res);
 }
 
 // Multi-peer batches over several engines (e == NULL; normally one engine per GPU,
@@ -3570,8 +2900,8 @@ struct EngineShare {
   bool on_driver = false;
 };
 
-static int multi_across(bool seal, uint32_t n, wg_tunn *const *tunn, const uint8_t *const *in, const uint32_t *len,
-                 uint8_t *const *dst, const uint32_t *dst_cap, wg_tunn_result *res) {
+static int multi_across(bool seal, const Knobs &kn, uint32_t n, wg_tunn *const *tunn, const uint8_t *const *in,
+                        const uint32_t *len, uint8_t *const *dst, const uint32_t *dst_cap, wg_tunn_result *res) {
   thread_local std::vector<EngineShare> shares;
   size_t used = 0, last = 0;
   for (uint32_t i = 0; i < n; ++i) {
@@ -3604,10 +2934,10 @@ static int multi_across(bool seal, uint32_t n, wg_tunn *const *tunn, const uint8
     S.dst.push_back(dst[i]);
     S.cap.push_back(dst_cap[i]);
   }
-  if (used == 1) return multi_on_engine(seal, shares[0].g, n, tunn, in, len, dst, dst_cap, res);
-  auto run_share = [seal](EngineShare &S) {
+  if (used == 1) return multi_on_engine(seal, kn, shares[0].g, n, tunn, in, len, dst, dst_cap, res);
+  auto run_share = [seal, &kn](EngineShare &S) {  // (kn: the caller's, which waits for every share)
     S.res.resize(S.idx.size());
-    return multi_on_engine(seal, S.g, (uint32_t)S.idx.size(), S.tunn.data(), S.in.data(), S.len.data(),
+    return multi_on_engine(seal, kn, S.g, (uint32_t)S.idx.size(), S.tunn.data(), S.in.data(), S.len.data(),
                            S.dst.data(), S.cap.data(), S.res.data());
   };
   for (size_t k = 0; k + 1 < used; ++k) {
@@ -3647,8 +2977,9 @@ int wg_tunn_encapsulate_multi(wg_engine *e, uint32_t n, wg_tunn *const *tunn,
   if (n && (!tunn || !src || !src_len || !dst || !dst_cap || !res))
     return wg_pipe_fail(WG_RC_INVALID_ARGUMENT, "encapsulate_multi: null", hipSuccess);
   if (n == 0) return WG_RC_OK;
-  if (!e) return multi_across(true, n, tunn, src, src_len, dst, dst_cap, res);
-  return multi_on_engine(true, e, n, tunn, src, src_len, dst, dst_cap, res);
+  const Knobs kn = read_knobs();
+  if (!e) return multi_across(true, kn, n, tunn, src, src_len, dst, dst_cap, res);
+  return multi_on_engine(true, kn, e, n, tunn, src, src_len, dst, dst_cap, res);
 }
 
 int wg_tunn_decapsulate_multi(wg_engine *e, uint32_t n, wg_tunn *const *tunn,
@@ -3657,8 +2988,9 @@ int wg_tunn_decapsulate_multi(wg_engine *e, uint32_t n, wg_tunn *const *tunn,
   if (n && (!tunn || !datagram || !len || !dst || !dst_cap || !res))
     return wg_pipe_fail(WG_RC_INVALID_ARGUMENT, "decapsulate_multi: null", hipSuccess);
   if (n == 0) return WG_RC_OK;
-  if (!e) return multi_across(false, n, tunn, datagram, len, dst, dst_cap, res);
-  return multi_on_engine(false, e, n, tunn, datagram, len, dst, dst_cap, res);
+  const Knobs kn = read_knobs();
+  if (!e) return multi_across(false, kn, n, tunn, datagram, len, dst, dst_cap, res);
+  return multi_on_engine(false, kn, e, n, tunn, datagram, len, dst, dst_cap, res);
 }
 
 int wg_tunn_decrypt_batch(wg_tunn *t, uint32_t n, const uint8_t *const *datagram,
@@ -3671,6 +3003,7 @@ int wg_tunn_decrypt_batch(wg_tunn *t, uint32_t n, const uint8_t *const *datagram
   Lease lease(t);
   if (lease.rc) return lease.rc;
   PhaseCall pc(t, n);
+  set_knobs(t, read_knobs());
   t->sc->sel.clear();
   t->sc->slot.clear();
   for (uint32_t i = 0; i < n; ++i) {

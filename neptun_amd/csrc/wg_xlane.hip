@@ -79,18 +79,7 @@ __device__ __forceinline__ bool xok(uint64_t a, uint32_t bytes, uint64_t lo, uin
 __device__ __forceinline__ uint4 xld16(const uint8_t *p, const XBounds &B) {
   return xok((uint64_t)p, 16u, B.in_lo, B.in_hi, B) ? ld16(p) : make_uint4(0, 0, 0, 0);
 }
-// a system-coherent 16-byte load (sc0 sc1: past the caches to memory): the resident
-// service's host-memory reads (kSys), made without a launch's cache invalidate
 typedef unsigned int xl_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ld16_sys(const uint8_t *p) {
-  // (a volatile global load: sc0 sc1 on gfx950, and the compiler places its waits)
-  const xl_u32x4 v =
-      *reinterpret_cast<const volatile __attribute__((address_space(1))) xl_u32x4 *>(reinterpret_cast<uint64_t>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ uint4 xld16_sys(const uint8_t *p, const XBounds &B) {
-  return xok((uint64_t)p, 16u, B.in_lo, B.in_hi, B) ? ld16_sys(p) : make_uint4(0, 0, 0, 0);
-}
 // a global-address-space 16-byte load: a flat load also counts against the LDS counter,
 // and the compiler then waits for every load at once (vmcnt(0) lgkmcnt(0)) where a
 // global one lets the key loads issued before the input be waited for alone
@@ -131,12 +120,11 @@ __device__ __forceinline__ void key_issue_scalar(const uint8_t *keys, const uint
   }
 }
 
-// Open's header (the packet's first 16 bytes, the nonce) the same way, for the launched
-// kernel only: a launch starts with the scalar cache invalidated, so it cannot hold an
-// earlier call's bytes (the resident service reads packets with vector loads past the
-// caches).  A half wave without a packet (exec) reads the other half's header: its lanes'
-// addresses are stale.  (Addresses are chosen before the loads, not loads under a branch:
-// a join's copy of the result waits for every scalar load.)
+// Open's header (the packet's first 16 bytes, the nonce) the same way: a launch starts
+// with the scalar cache invalidated, so it cannot hold an earlier call's bytes.  A half
+// wave without a packet (exec) reads the other half's header: its lanes' addresses are
+// stale.  (Addresses are chosen before the loads, not loads under a branch: a join's copy
+// of the result waits for every scalar load.)
 template <uint32_t G>
 __device__ __forceinline__ void hdr_issue_scalar(const uint8_t *src, uint4 (&hr)[2]) {
   static_assert(G == 64u || G == 32u, "one or two groups per wave");
@@ -191,8 +179,7 @@ __device__ __forceinline__ F26 f26_zero() {
 // C 64-byte blocks apart: over PCIe each piece is a request of its own.  50 packets of
 // 1350 B from 8 concurrent callers are then ~0.9 G read requests and as many 16-byte
 // writes per second -- with their headers about the whole upstream PCIe link, where 8
-// callers flattened at 54 Gbit/s with launches and with the resident service alike
-// (profiles/r06n/tt_*).  Staged, the group moves its packet through LDS: its G lanes
+// callers flattened at 54 Gbit/s (profiles/r06n/tt_*).  Staged, the group moves its packet through LDS: its G lanes
 // load consecutive pieces (one load instruction covers G x 16 contiguous bytes, which
 // the memory pipeline merges), every lane then reads and writes its blocks in LDS, and
 // the group stores the output the same contiguous way -- the same bytes in 4-8x fewer,
@@ -211,13 +198,12 @@ __device__ __forceinline__ void lds_wave_sync() { asm volatile("s_waitcnt lgkmcn
 // packet's offsets OR-ed (misaligned -> WG_STATUS_MISALIGNED); st: its status (or null).
 // kStage: through the group's LDS region gb (stage_cap<G>() pieces; the caller checks
 // that the packet's (P + 31) / 16 pieces fit).
-template <bool kSeal, uint32_t G, bool kStage = false, bool kSys = false>
+template <bool kSeal, uint32_t G, bool kStage = false>
 __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uint8_t *dst, uint32_t len,
                                              uint32_t slot, uint64_t counter, uint64_t align, int32_t *st,
                                              const uint8_t *keys, const uint32_t *key_index, uint32_t key_slots,
-                                             uint32_t pkt, uint4 *gb = nullptr, uint64_t *stamps = nullptr) {
-  // (stamps: the service's phase stamps of this packet, its group's lane 0 writes them)
-  const bool stamp = stamps && l == 0u;
+                                             uint32_t pkt, uint4 *gb = nullptr) {
+  const bool lane0 = l == 0u;  // (the group's lane that writes its packet's status and seal's header)
   int32_t status = WG_STATUS_OK;
   if (!kSeal && slot == WG_KEY_SLOT_INVALID_PACKET) status = WG_STATUS_INVALID_PACKET;
   else if (!kSeal && slot == WG_KEY_SLOT_NO_SESSION) status = WG_STATUS_NO_CURRENT_SESSION;
@@ -230,7 +216,7 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
   const uint32_t out_bytes = kSeal ? len + WG_DATA_OVERHEAD_SZ : (len >= WG_DATA_OVERHEAD_SZ ? len - WG_DATA_OVERHEAD_SZ : 0u);
   const XBounds B{(uint64_t)src, (uint64_t)src + in_bytes, (uint64_t)dst, (uint64_t)dst + out_bytes, pkt, l};
   if (status != WG_STATUS_OK) {  // group-uniform: nothing of the packet is read or written
-    if (l == 0u && st) *st = status;
+    if (lane0 && st) *st = status;
     return;
   }
 
@@ -264,9 +250,7 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
   uint4 sv[kBatch];
   uint32_t key[8];
   uint32_t sidx = 0, n1 = 0, n2 = 0;
-  // (the service's open reads its header with a vector load past the caches, and waits for
-  // it -- and so for the input -- before its first block)
-  constexpr bool kScalarKey = kStage && G >= 32u && (kSeal || !kSys) && WG_XLANE_SCALAR_KEY;
+  constexpr bool kScalarKey = kStage && G >= 32u && WG_XLANE_SCALAR_KEY;
   uint32_t kr[2][9];  // (kScalarKey: each half wave's key and index, and open's header)
   uint4 hr[2];
   auto header_checks = [&](const uint4 &h) {  // header: type, receiver_idx, counter (mod.rs:170-180)
@@ -288,7 +272,7 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
       key[0] = a.x; key[1] = a.y; key[2] = a.z; key[3] = a.w;
       key[4] = b.x; key[5] = b.y; key[6] = b.z; key[7] = b.w;
       sidx = key_index[slot];
-      if constexpr (!kSeal) header_checks(kSys ? xld16_sys(src, B) : kStage ? xld16_g(src, B) : xld16(src, B));
+      if constexpr (!kSeal) header_checks(kStage ? xld16_g(src, B) : xld16(src, B));
     }
   };
   // (kScalarKey, after the input's loads: a scheduling barrier and an empty asm per value,
@@ -328,7 +312,7 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
 #pragma unroll
       for (uint32_t k = 0; k < kBatch; ++k) {
         const uint32_t p = l + k * G, pp = p < np_in ? p : np_in - 1u;
-        sv[k] = kSys ? xld16_sys(in + 16u * pp, B) : xld16_g(in + 16u * pp, B);
+        sv[k] = xld16_g(in + 16u * pp, B);
       }
     }
   } else {
@@ -371,7 +355,7 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
 #pragma unroll
       for (uint32_t k = 0; k < kBatch; ++k) {
         const uint32_t p = p0 + l + k * G;
-        sv[k] = p < np_in ? (kSys ? xld16_sys(in + 16u * p, B) : xld16_g(in + 16u * p, B)) : make_uint4(0, 0, 0, 0);
+        sv[k] = p < np_in ? xld16_g(in + 16u * p, B) : make_uint4(0, 0, 0, 0);
       }
 #pragma unroll
       for (uint32_t k = 0; k < kBatch; ++k) {
@@ -380,7 +364,6 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
       }
     }
     lds_wave_sync();
-    if (stamp) stamps[1] = wall_clock64();
     if (any) load_block(b0, x);
     if (!kSeal && l == Lu - 1u) {  // (before this lane's last block overwrites the tag's first bytes)
       const uint4 ta = gb[P >> 4], tb = (P & 15u) ? gb[(P >> 4) + 1u] : make_uint4(0, 0, 0, 0);
@@ -485,7 +468,6 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
       if (bad && wr) status = WG_STATUS_INVALID_AEAD_TAG;
     }
     lds_wave_sync();
-    if (stamp) stamps[2] = wall_clock64();
     if (wr) {
       const uint32_t nb_out = kSeal ? P + 16u : P, np_out = (nb_out + 15u) / 16u;
       for (uint32_t p = l; p < np_out; p += G) {
@@ -498,11 +480,10 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
           xstore_partial(out + o, yw, (int)(nb_out - o), B);
         }
       }
-      if (kSeal && l == 0u) xst16(dst, WG_MSG_DATA, sidx, n1, n2, B);  // header (session.rs:224-229)
+      if (kSeal && lane0) xst16(dst, WG_MSG_DATA, sidx, n1, n2, B);  // header (session.rs:224-229)
     }
-    if (stamp) stamps[3] = wall_clock64();
   } else if (kSeal) {
-    if (l == 0u) xst16(dst, WG_MSG_DATA, sidx, n1, n2, B);  // header (session.rs:224-229)
+    if (lane0) xst16(dst, WG_MSG_DATA, sidx, n1, n2, B);  // header (session.rs:224-229)
   } else {
     bad = gshfl<G>(bad, Lu - 1u);
     if (bad && wr) {
@@ -518,7 +499,7 @@ __device__ __forceinline__ void xlane_packet(uint32_t l, const uint8_t *src, uin
       }
     }
   }
-  if (l == 0u && st) *st = status;
+  if (lane0 && st) *st = status;
 }
 
 // The grid's completion word (DescParams::done_flag): each wave waits for its own
@@ -601,134 +582,6 @@ __global__ __launch_bounds__(kXlaneThreads) void aead_xlane_strided_kernel(Strid
   xlane_packet<kSeal, G>(l, prm.src + (uint64_t)i * prm.src_stride, prm.dst + (uint64_t)i * prm.dst_stride, prm.len,
                          prm.key_slot, prm.counter_base + i, 0u, prm.status ? prm.status + i : nullptr, prm.keys,
                          prm.key_index, 0xffffffffu, i);
-}
-
-// ---------------------------------------------------------------------------
-// Resident service (wg_aead_kernels.h SrvSlot; host side wg_tunn.cpp Service).
-// NepTUN's workers hand the data plane at most 50 packets at a time from every
-// physical core (packet_workers.rs:27, :113-131).  As launches, concurrent calls of
-// this size queue on the process's hardware queues (~13 us of queue time each: 8
-// callers ran 54 Gbit/s); posted to this kernel's slots, a call costs
-// its PCIe round trips and no launch.
-// ---------------------------------------------------------------------------
-namespace {
-
-// {seq, op, n, G} of a slot in one system-coherent 16-byte load (the host writes seq
-// last, so a new seq comes with its own op / n / G)
-typedef unsigned int srv_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 srv_poll(const SrvSlot *sl) {
-  srv_u32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)"
-               : "=v"(v)
-               : "v"(reinterpret_cast<uint64_t>(sl))
-               : "memory");
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// this workgroup's packets of the request (lane: its index among the slot's lanes)
-template <bool kSeal, uint32_t G>
-__device__ __forceinline__ void srv_packets(SrvSlot *sl, uint32_t lane, uint32_t n, const SrvParams &p,
-                                            uint4 *stage) {
-  const uint32_t l = lane & (G - 1u);
-  uint4 *gb = stage + ((lane % kXlaneThreads) / G) * stage_cap<G>();
-  for (uint32_t i = lane / G; i < n; i += kSrvLanes / G) {  // (group-uniform)
-    // the descriptor, past the caches (the host rewrote the slot since the last request)
-    const uint4 d0 = ld16_sys(reinterpret_cast<const uint8_t *>(&sl->d[i]));
-    const uint4 d1 = ld16_sys(reinterpret_cast<const uint8_t *>(&sl->d[i]) + 16u);
-    const uint64_t so = (uint64_t)d0.x | ((uint64_t)d0.y << 32), dn = (uint64_t)d0.z | ((uint64_t)d0.w << 32);
-    const uint64_t ctr = (uint64_t)d1.x | ((uint64_t)d1.y << 32);
-    const uint32_t len = d1.z, kslot = d1.w;
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(so);
-    uint8_t *dst = reinterpret_cast<uint8_t *>(dn);
-    uint64_t *stamps = p.stamp && i == 0u ? sl->stamp + 5 : nullptr;  // (packet 0: stamp[5 ..])
-    if (stamps && l == 0u) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      stamps[0] = wall_clock64();
-    }
-    if (stage_fits<kSeal, G>(len)) {
-      xlane_packet<kSeal, G, true, true>(l, src, dst, len, kslot, ctr, so | dn, sl->st + i, p.keys, p.key_index,
-                                         p.key_slots, i, gb, stamps);
-    } else {  // (its plain loads: first drop what the caches hold of earlier requests)
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-      xlane_packet<kSeal, G>(l, src, dst, len, kslot, ctr, so | dn, sl->st + i, p.keys, p.key_index, p.key_slots, i);
-    }
-  }
-}
-
-}  // namespace
-
-__global__ __launch_bounds__(kXlaneThreads) void xlane_service_kernel(SrvParams p) {
-  __shared__ uint32_t s_req[5];
-  __shared__ uint4 stage[kXlaneStagePieces];
-  const uint32_t slot = blockIdx.x / kSrvGroup, part = blockIdx.x % kSrvGroup;
-  SrvSlot *sl = p.slots + slot;
-  const uint64_t t0 = wall_clock64();
-  // the last request of this slot the host saw done (it posts the next one only then)
-  uint32_t last = 0;
-  if (threadIdx.x == 0u) last = __hip_atomic_load(&sl->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  for (;;) {
-    if (threadIdx.x == 0u) {
-      uint32_t go = 0u;
-      uint4 h = make_uint4(last, 0u, 0u, 0u);
-      for (uint32_t i = 0;; ++i) {
-        h = srv_poll(sl);
-        if (h.x != last) {
-          go = 1u;
-          break;
-        }
-        if ((i & 15u) == 0u && (__hip_atomic_load(p.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u ||
-                                wall_clock64() - t0 > p.lease_ticks))
-          break;
-        __builtin_amdgcn_s_sleep(1);
-      }
-      s_req[0] = go;
-      s_req[1] = h.x;
-      s_req[2] = h.y;
-      s_req[3] = h.z;
-      s_req[4] = h.w;
-    }
-    __syncthreads();
-    const uint32_t go = s_req[0], seq = s_req[1], op = s_req[2], n = s_req[3], G = s_req[4];
-    __syncthreads();  // (s_req is rewritten by the next poll)
-    if (!go) return;  // (workgroup-uniform: stop or lease)
-    const bool stamp = p.stamp && part == 0u && threadIdx.x == 0u;
-    if (stamp) sl->stamp[0] = wall_clock64();
-    // (the request's bytes -- descriptors, packets -- are read past the caches; no
-    // per-request invalidate: with a slot's workgroups on many CUs it cost 3-4 us a
-    // request under load, profiles/r06r)
-    if (stamp) sl->stamp[1] = wall_clock64();
-    const uint32_t lane = part * kXlaneThreads + threadIdx.x;
-    if (n <= kSrvDescs && n * G <= kSrvLanes) {  // (the host never posts more)
-      switch ((op ? 128u : 0u) | G) {
-        case 128u | 64u: srv_packets<true, 64>(sl, lane, n, p, stage); break;
-        case 128u | 32u: srv_packets<true, 32>(sl, lane, n, p, stage); break;
-        case 128u | 16u: srv_packets<true, 16>(sl, lane, n, p, stage); break;
-        case 128u | 8u: srv_packets<true, 8>(sl, lane, n, p, stage); break;
-        case 64u: srv_packets<false, 64>(sl, lane, n, p, stage); break;
-        case 32u: srv_packets<false, 32>(sl, lane, n, p, stage); break;
-        case 16u: srv_packets<false, 16>(sl, lane, n, p, stage); break;
-        case 8u: srv_packets<false, 8>(sl, lane, n, p, stage); break;
-        default: break;
-      }
-    }
-    // arrival: this workgroup's outputs and statuses acknowledged, one system-scope
-    // release each; the last of the slot's workgroups publishes seq (grid_done's shape)
-    if (stamp) sl->stamp[2] = wall_clock64();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (stamp) sl->stamp[3] = wall_clock64();
-    if (threadIdx.x == 0u) {
-      uint32_t *cnt = p.d_count + (threadIdx.x + slot * 32u);
-      const uint32_t prev = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      if (prev == kSrvGroup - 1u) {
-        if (p.stamp) sl->stamp[4] = wall_clock64();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-        __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&sl->done + threadIdx.x, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      last = seq;
-    }
-  }
 }
 
 template __global__ void aead_xlane_kernel<true, 64>(DescParams);

@@ -112,6 +112,8 @@ def main():
         e, d = statistics.median(te), statistics.median(td)
         print(json.dumps({"packets": n, "P": P, "registered": a.register, "verified": ok,
                           "encap_ms": round(e * 1e3, 3), "decap_ms": round(d * 1e3, 3),
+                          "encap_ms_reps": [round(x * 1e3, 3) for x in te],
+                          "decap_ms_reps": [round(x * 1e3, 3) for x in td],
                           "encap_gbps": round(n * P * 8 / e / 1e9, 1),
                           "decap_gbps": round(n * P * 8 / d / 1e9, 1),
                           "roundtrip_gbps": round(n * P * 8 / (e + d) / 1e9, 1),
