@@ -475,6 +475,87 @@ int wg_gpu_route_batch(wg_gpu_ctx *ctx, wg_packet_desc *descs, uint32_t n, const
                        void *stream);
 
 /*
+ * AllowedIPs: outbound routing by destination prefix, inbound source filter.
+ * NepTUN routes every packet read from the TUN by longest-prefix match of its
+ * destination address (device/mod.rs:1295-1313: Tunn::dst_address,
+ * noise/mod.rs:205-223, then AllowedIps::find, device/allowed_ips.rs:49) and
+ * writes a decrypted packet to the TUN only if peer.is_allowed_ip(source)
+ * (device/mod.rs:1056, packet_workers.rs:270, peer.rs:178).  It keeps two
+ * relations, and they can disagree; a wg_allowed table keeps both:
+ *   the route      network -> value, the last insert of a network wins
+ *                  (Device::peers_by_ip);
+ *   the ownership  the set of (network, value) pairs (each Peer's allowed_ips).
+ * `value` is the caller's: a peer number, a Tunn number, a key slot.  0xFFFFFFFF
+ * is reserved (WG_ALLOWED_NONE = no route).  family is 4 or 6; addr holds 4
+ * (family 4) or 16 bytes in network order.  IPv4 and IPv6 are separate tables
+ * (no v4-mapped handling); prefix length 0 is a legal default route.
+ *   wg_allowed_insert        host bits are cleared (IpNetwork::new_truncate,
+ *                            allowed_ips.rs:45); cidr > 32 / > 128 is refused.
+ *                            Sets the network's route to `value` and adds
+ *                            (network, value) to the ownership.
+ *   wg_allowed_remove_value  drops every ownership pair of `value` and every
+ *                            route whose CURRENT value is `value`
+ *                            (device/mod.rs:533-534, :564).  So after A and then
+ *                            B inserted one network, removing B leaves the
+ *                            network without a route while A still owns it.
+ *   wg_allowed_clear         empties both relations.
+ *   wg_allowed_count         routed networks, both families.
+ *   wg_allowed_find          *value = the route of the longest routed network
+ *                            containing addr, else WG_ALLOWED_NONE.
+ *   wg_allowed_contains      1 if any network owned by `value` contains addr,
+ *                            else 0 (negative: a wg_rc).  May differ from
+ *                            find(addr) == value where prefixes nest or collide.
+ * The table needs no GPU and has its own lock.  Lookups walk a flat image of the
+ * table, rebuilt on the first lookup after a change; the device walks a copy of
+ * the same image with the same code:
+ *   wg_gpu_allowed_set          uploads a's current image and swaps it in (as
+ *                               wg_gpu_route_set does; later changes of `a` need
+ *                               another call).  a == NULL removes the image;
+ *                               with none every lookup yields WG_ALLOWED_NONE /
+ *                               not allowed.
+ *   wg_gpu_allowed_route_batch  per descriptor: the plaintext IP packet at
+ *                               src + src_off (len bytes, any byte alignment;
+ *                               nothing outside it is read), its destination
+ *                               address -- version nibble byte0 >> 4; 4 with
+ *                               len >= 20: bytes 16..20; 6 with len >= 40: bytes
+ *                               24..40; else none -- and find().  Writes
+ *                               value_out[i] (device uint32, may be NULL) and,
+ *                               if set_key_slot != 0, descs[i].key_slot = value:
+ *                               WG_ALLOWED_NONE then makes the seal kernels
+ *                               answer WG_STATUS_BAD_KEY_SLOT and write nothing.
+ *                               descs[i].counter is not touched.
+ *   wg_gpu_allowed_filter_batch after an open: for packet i with status[i] ==
+ *                               WG_STATUS_OK and len > 32, the plaintext at
+ *                               dst + dst_off (len - 32 bytes), its source
+ *                               address -- 4 with >= 20 bytes: bytes 12..16; 6
+ *                               with >= 40: bytes 8..24 -- and allowed_out[i] =
+ *                               contains(source, e) ? 1 : 0 with e = expect[i],
+ *                               or descs[i].key_slot >> slot_shift when expect is
+ *                               NULL (a Tunn owns 16 slots: shift 4 gives its
+ *                               number).  Every other packet gets 0.  allowed_out
+ *                               is a device uint8 array; status and allowed_out
+ *                               must not be NULL.
+ */
+#define WG_ALLOWED_NONE 0xFFFFFFFFu
+typedef struct wg_allowed wg_allowed;
+int wg_allowed_create(wg_allowed **out);
+int wg_allowed_destroy(wg_allowed *a);
+int wg_allowed_insert(wg_allowed *a, int family, const uint8_t addr[16], uint32_t cidr,
+                      uint32_t value);
+int wg_allowed_remove_value(wg_allowed *a, uint32_t value);
+int wg_allowed_clear(wg_allowed *a);
+uint32_t wg_allowed_count(const wg_allowed *a);
+int wg_allowed_find(wg_allowed *a, int family, const uint8_t addr[16], uint32_t *value);
+int wg_allowed_contains(wg_allowed *a, int family, const uint8_t addr[16], uint32_t value);
+int wg_gpu_allowed_set(wg_gpu_ctx *ctx, wg_allowed *a);
+int wg_gpu_allowed_route_batch(wg_gpu_ctx *ctx, wg_packet_desc *descs, uint32_t n,
+                               const uint8_t *src, uint32_t *value_out, int set_key_slot,
+                               void *stream);
+int wg_gpu_allowed_filter_batch(wg_gpu_ctx *ctx, const wg_packet_desc *descs, uint32_t n,
+                                const uint8_t *dst, const int32_t *status, const uint32_t *expect,
+                                uint32_t slot_shift, uint8_t *allowed_out, void *stream);
+
+/*
  * Host-resident batches (the real data path: TUN read buffers in, UDP send
  * buffers out and vice versa).  A pipe owns `depth` streams and device staging
  * buffers of `chunk_bytes` each; a call splits the batch into chunks and runs

@@ -60,6 +60,9 @@ enum wg_tunn_kind {
   WG_TUNN_WRITE_TO_NETWORK = 2,  /* datagram of `len` bytes at dst */
   WG_TUNN_WRITE_TO_TUNNEL = 3,   /* IP packet of `len` bytes at dst, source address src_ip */
   WG_TUNN_NOT_DATA = 4,          /* handshake / cookie message: hand it to the CPU Tunn */
+  WG_TUNN_SKIPPED = 5,           /* IfaceReadResult::Skip: no route for the packet (routed
+                                    encapsulate) / not written to the TUN: the source is not
+                                    one of the peer's AllowedIPs (filtered decapsulate) */
 };
 
 typedef struct wg_tunn_result {
@@ -203,6 +206,35 @@ int wg_tunn_encapsulate_multi(wg_engine *e, uint32_t n, wg_tunn *const *tunn,
 int wg_tunn_decapsulate_multi(wg_engine *e, uint32_t n, wg_tunn *const *tunn,
                               const uint8_t *const *datagram, const uint32_t *len,
                               uint8_t *const *dst, const uint32_t *dst_cap, wg_tunn_result *res);
+/* The multi-peer batches with the peer chosen / checked by an AllowedIPs table
+ * (wg_allowed, include/neptun_gpu.h) whose values index peers[0 .. npeers):
+ *   wg_tunn_encapsulate_routed: read_packet's routing (device/mod.rs:1295-1313) in
+ *     front of wg_tunn_encapsulate_multi.  value[i] = find(dst_address(src[i])) on
+ *     the host (over the engine's pool threads; a small batch, or e == NULL, on the
+ *     caller's).  A packet with no destination address, no route, value >= npeers
+ *     or a NULL peers[value] comes back WG_TUNN_SKIPPED (status 0, len 0): it takes
+ *     no counter and adds nothing to tx_bytes.  The others go, in batch order,
+ *     through ONE wg_tunn_encapsulate_multi call with tunn = peers[value] (none if
+ *     every packet is skipped), so their results equal the sequential calls.
+ *     value_out (n host uint32, may be NULL) receives value[i] (WG_ALLOWED_NONE:
+ *     no address or no route).
+ *   wg_tunn_decapsulate_multi_allowed: wg_tunn_decapsulate_multi with tunn[i] =
+ *     peers[value[i]] (any value[i] >= npeers or NULL peer: WG_RC_INVALID_ARGUMENT,
+ *     nothing done), then every WG_TUNN_WRITE_TO_TUNNEL result whose src_ip fails
+ *     contains(src_ip, value[i]) becomes WG_TUNN_SKIPPED with len, ip_version and
+ *     src_ip kept (device/mod.rs:1056: the packet is dropped after decapsulate ran,
+ *     so rx_bytes, the replay window and the current session are exactly those of
+ *     the unfiltered call).
+ * e == NULL behaves as in the multi calls. */
+int wg_tunn_encapsulate_routed(wg_engine *e, wg_allowed *a, wg_tunn *const *peers, uint32_t npeers,
+                               uint32_t n, const uint8_t *const *src, const uint32_t *src_len,
+                               uint8_t *const *dst, const uint32_t *dst_cap, wg_tunn_result *res,
+                               uint32_t *value_out);
+int wg_tunn_decapsulate_multi_allowed(wg_engine *e, wg_allowed *a, wg_tunn *const *peers,
+                                      uint32_t npeers, uint32_t n, const uint32_t *value,
+                                      const uint8_t *const *datagram, const uint32_t *len,
+                                      uint8_t *const *dst, const uint32_t *dst_cap,
+                                      wg_tunn_result *res);
 /* n x Tunn::decrypt(datagram[i], dst[i]) (feature "xray", mod.rs:383-417 ->
  * Session::decrypt_data_packet session.rs:316-353): the first session whose
  * receiving OR sending index equals the header's receiver_idx, opened with the

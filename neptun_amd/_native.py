@@ -76,6 +76,18 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.wg_gpu_cookie_reply_open_batch.argtypes = [vp, u32, vp, vp, vp]
     L.wg_gpu_route_set.argtypes = [vp, u32, vp, vp]
     L.wg_gpu_route_batch.argtypes = [vp, vp, u32, vp, vp]
+    L.wg_allowed_create.argtypes = [c.POINTER(vp)]
+    L.wg_allowed_destroy.argtypes = [vp]
+    L.wg_allowed_insert.argtypes = [vp, c.c_int, c.c_char_p, u32, u32]
+    L.wg_allowed_remove_value.argtypes = [vp, u32]
+    L.wg_allowed_clear.argtypes = [vp]
+    L.wg_allowed_count.argtypes = [vp]
+    L.wg_allowed_count.restype = u32
+    L.wg_allowed_find.argtypes = [vp, c.c_int, c.c_char_p, c.POINTER(u32)]
+    L.wg_allowed_contains.argtypes = [vp, c.c_int, c.c_char_p, u32]
+    L.wg_gpu_allowed_set.argtypes = [vp, vp]
+    L.wg_gpu_allowed_route_batch.argtypes = [vp, vp, u32, vp, vp, c.c_int, vp]
+    L.wg_gpu_allowed_filter_batch.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp]
     L.wg_gpu_pipe_create.argtypes = [vp, u64, u32, c.POINTER(vp)]
     L.wg_gpu_pipe_destroy.argtypes = [vp]
     L.wg_gpu_pipe_seal_strided.argtypes = [vp, u32, u32, u32, u64, vp, u64, vp, u64, vp]

@@ -20,6 +20,7 @@
 
 #include "neptun_gpu.h"
 #include "wg_aead_kernels.h"
+#include "wg_allowed.h"
 
 struct wg_gpu_ctx {
   int device = 0;
@@ -28,6 +29,8 @@ struct wg_gpu_ctx {
   uint32_t *d_key_index = nullptr; // key_slots
   uint2 *d_route = nullptr;        // receiver_idx -> key slot (wg_route.hip), 2^route_bits
   uint32_t route_bits = 0;
+  wg::AllowedWord *d_allowed = nullptr;  // AllowedIPs image (wg_allowed.h): slots | heads | owners
+  wg::AllowedView allowed;         // device pointers into d_allowed (all zero: no image)
   uint32_t cus = 0;                // compute units (persistent strided grid)
   bool pad_slots = false;          // wg_gpu_ctx_set_slot_padding
   int64_t xlane_lanes = -1;        // wg_gpu_ctx_set_xlane_lanes (< 0: default)
@@ -87,6 +90,7 @@ struct DeviceGuard {
 
 // shared with wg_pipe.cpp / wg_tunn.cpp
 int wg_pipe_fail(int rc, const char *what, hipError_t e) { return fail(rc, what, e); }
+int wg_fail_msg(int rc, const char *what) { return fail(rc, what); }  // wg_allowed.cpp
 int wg_ctx_device(const wg_gpu_ctx *ctx) { return ctx->device; }
 bool wg_ctx_slot_padding(const wg_gpu_ctx *ctx) { return ctx->pad_slots; }
 // a Tunn's key slots: claimed at create (an overlap with a live Tunn's range on this
@@ -222,6 +226,7 @@ int wg_gpu_ctx_destroy(wg_gpu_ctx *ctx) {
   (void)hipFree(ctx->d_keys);
   (void)hipFree(ctx->d_key_index);
   (void)hipFree(ctx->d_route);
+  (void)hipFree(ctx->d_allowed);
   // (through the shared pins: another context may still hold the same range)
   for (const auto &r : ctx->reg) (void)pin_release(r.host);
   delete ctx;
@@ -789,6 +794,70 @@ int wg_gpu_route_batch(wg_gpu_ctx *ctx, wg_packet_desc *descs, uint32_t n, const
   hipLaunchKernelGGL(wg::route_kernel, dim3((n + 255u) / 256u), dim3(256), 0,
                      static_cast<hipStream_t>(stream), descs, n, src, ctx->d_route, ctx->route_bits);
   WG_HIP(hipGetLastError(), "route_batch: launch");
+  return WG_RC_OK;
+}
+
+int wg_gpu_allowed_set(wg_gpu_ctx *ctx, wg_allowed *a) {
+  if (!ctx) return fail(WG_RC_INVALID_ARGUMENT, "allowed_set: null context");
+  std::shared_ptr<const wg::AllowedImage> img;
+  if (a && !(img = wg::allowed_image(a)))
+    return fail(WG_RC_OUT_OF_MEMORY, "allowed_set: the table's image is too large");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard g(ctx->device);
+  wg::AllowedWord *d = nullptr;
+  wg::AllowedView v;
+  if (img && !img->words.empty()) {
+    const size_t bytes = img->words.size() * sizeof(wg::AllowedWord);
+    WG_HIP(hipMalloc(&d, bytes), "allowed_set: device alloc");
+    hipError_t e = hipMemcpy(d, img->words.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return fail(WG_RC_HIP_ERROR, "allowed_set: copy", e);
+    }
+    v = img->view;
+    v.slots = d;
+    v.heads = d + img->heads_at;
+    v.owners = d + img->owners_at;
+  }
+  // launches already queued may still read the old image
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return fail(WG_RC_HIP_ERROR, "allowed_set: sync", e);
+  }
+  (void)hipFree(ctx->d_allowed);
+  ctx->d_allowed = d;
+  ctx->allowed = v;
+  return WG_RC_OK;
+}
+
+int wg_gpu_allowed_route_batch(wg_gpu_ctx *ctx, wg_packet_desc *descs, uint32_t n, const uint8_t *src,
+                               uint32_t *value_out, int set_key_slot, void *stream) {
+  if (!ctx || (n && (!descs || !src)))
+    return fail(WG_RC_INVALID_ARGUMENT, "allowed_route_batch: null argument");
+  if (n == 0) return WG_RC_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);  // the image is swapped by allowed_set
+  DeviceGuard g(ctx->device);
+  hipLaunchKernelGGL(wg::allowed_route_kernel, dim3((n + 255u) / 256u), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), descs, n, src, ctx->allowed, value_out,
+                     set_key_slot ? 1u : 0u);
+  WG_HIP(hipGetLastError(), "allowed_route_batch: launch");
+  return WG_RC_OK;
+}
+
+int wg_gpu_allowed_filter_batch(wg_gpu_ctx *ctx, const wg_packet_desc *descs, uint32_t n,
+                                const uint8_t *dst, const int32_t *status, const uint32_t *expect,
+                                uint32_t slot_shift, uint8_t *allowed_out, void *stream) {
+  if (!ctx || (n && (!descs || !dst || !status || !allowed_out)))
+    return fail(WG_RC_INVALID_ARGUMENT, "allowed_filter_batch: null argument");
+  if (slot_shift > 31u) return fail(WG_RC_INVALID_ARGUMENT, "allowed_filter_batch: slot_shift above 31");
+  if (n == 0) return WG_RC_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipLaunchKernelGGL(wg::allowed_filter_kernel, dim3((n + 255u) / 256u), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), descs, n, dst, status, expect, slot_shift,
+                     ctx->allowed, allowed_out);
+  WG_HIP(hipGetLastError(), "allowed_filter_batch: launch");
   return WG_RC_OK;
 }
 

@@ -47,6 +47,7 @@
 #include "neptun_gpu.h"
 #include "neptun_tunn.h"
 #include "wg_aead_kernels.h"
+#include "wg_allowed.h"
 
 int wg_pipe_fail(int rc, const char *what, hipError_t e);  // wg_gpu.cpp
 int wg_ctx_device(const wg_gpu_ctx *ctx);                   // wg_gpu.cpp
@@ -2991,6 +2992,99 @@ int wg_tunn_decapsulate_multi(wg_engine *e, uint32_t n, wg_tunn *const *tunn,
   const Knobs kn = read_knobs();
   if (!e) return multi_across(false, kn, n, tunn, datagram, len, dst, dst_cap, res);
   return multi_on_engine(false, kn, e, n, tunn, datagram, len, dst, dst_cap, res);
+}
+
+// read_packet's routing (device/mod.rs:1295-1313) in front of the multi-peer
+// encapsulate: the table's image walked on the host (the walker of wg_allowed.h, over
+// the engine's pool from 2 x WG_TUNN_GRAIN_LIGHT packets), the routed packets
+// compacted in batch order into one wg_tunn_encapsulate_multi call
+int wg_tunn_encapsulate_routed(wg_engine *e, wg_allowed *a, wg_tunn *const *peers, uint32_t npeers,
+                               uint32_t n, const uint8_t *const *src, const uint32_t *src_len,
+                               uint8_t *const *dst, const uint32_t *dst_cap, wg_tunn_result *res,
+                               uint32_t *value_out) {
+  if (!a || (npeers && !peers) || (n && (!src || !src_len || !dst || !dst_cap || !res)))
+    return wg_pipe_fail(WG_RC_INVALID_ARGUMENT, "encapsulate_routed: null", hipSuccess);
+  if (n == 0) return WG_RC_OK;
+  const auto img = wg::allowed_image(a);
+  if (!img) return wg_pipe_fail(WG_RC_OUT_OF_MEMORY, "encapsulate_routed: the table's image is too large", hipSuccess);
+  std::vector<uint32_t> local;
+  if (!value_out) {
+    local.resize(n);
+    value_out = local.data();
+  }
+  const std::function<void(size_t, size_t)> walk = [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      wg::AllowedAddr ad;
+      const uint32_t fam = src[i] ? wg::allowed_packet_addr(src[i], src_len[i], false, ad) : 0u;
+      value_out[i] = fam ? wg::allowed_find(img->view, fam == 6u, ad) : WG_ALLOWED_NONE;
+    }
+  };
+  if (e && e->pool)
+    e->pool->run(n, walk, grain_light());
+  else
+    walk(0, n);
+  std::vector<uint32_t> idx;
+  std::vector<wg_tunn *> tunn;
+  idx.reserve(n);
+  tunn.reserve(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t v = value_out[i];
+    if (v < npeers && peers[v]) {
+      idx.push_back(i);
+      tunn.push_back(peers[v]);
+    } else {
+      res[i] = wg_tunn_result{};
+      res[i].kind = WG_TUNN_SKIPPED;
+    }
+  }
+  const uint32_t m = (uint32_t)idx.size();
+  if (m == 0) return WG_RC_OK;
+  if (m == n) return wg_tunn_encapsulate_multi(e, n, tunn.data(), src, src_len, dst, dst_cap, res);
+  std::vector<const uint8_t *> c_src(m);
+  std::vector<uint8_t *> c_dst(m);
+  std::vector<uint32_t> c_len(m), c_cap(m);
+  std::vector<wg_tunn_result> c_res(m);
+  for (uint32_t j = 0; j < m; ++j) {
+    c_src[j] = src[idx[j]];
+    c_len[j] = src_len[idx[j]];
+    c_dst[j] = dst[idx[j]];
+    c_cap[j] = dst_cap[idx[j]];
+  }
+  const int rc = wg_tunn_encapsulate_multi(e, m, tunn.data(), c_src.data(), c_len.data(), c_dst.data(),
+                                           c_cap.data(), c_res.data());
+  for (uint32_t j = 0; j < m; ++j) res[idx[j]] = c_res[j];
+  return rc;
+}
+
+// the multi-peer decapsulate, then peer.is_allowed_ip(source) (device/mod.rs:1056)
+// over its results: the Tunns have already seen every packet
+int wg_tunn_decapsulate_multi_allowed(wg_engine *e, wg_allowed *a, wg_tunn *const *peers,
+                                      uint32_t npeers, uint32_t n, const uint32_t *value,
+                                      const uint8_t *const *datagram, const uint32_t *len,
+                                      uint8_t *const *dst, const uint32_t *dst_cap,
+                                      wg_tunn_result *res) {
+  if (!a || (npeers && !peers) || (n && (!value || !datagram || !len || !dst || !dst_cap || !res)))
+    return wg_pipe_fail(WG_RC_INVALID_ARGUMENT, "decapsulate_multi_allowed: null", hipSuccess);
+  if (n == 0) return WG_RC_OK;
+  std::vector<wg_tunn *> tunn(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (value[i] >= npeers || !peers[value[i]])
+      return wg_pipe_fail(WG_RC_INVALID_ARGUMENT, "decapsulate_multi_allowed: a value names no peer", hipSuccess);
+    tunn[i] = peers[value[i]];
+  }
+  const auto img = wg::allowed_image(a);
+  if (!img)
+    return wg_pipe_fail(WG_RC_OUT_OF_MEMORY, "decapsulate_multi_allowed: the table's image is too large", hipSuccess);
+  const int rc = wg_tunn_decapsulate_multi(e, n, tunn.data(), datagram, len, dst, dst_cap, res);
+  for (uint32_t i = 0; i < n; ++i) {
+    wg_tunn_result &r = res[i];
+    if (r.kind != WG_TUNN_WRITE_TO_TUNNEL) continue;
+    const bool v6 = r.ip_version == 6;
+    wg::AllowedAddr ad;
+    for (int k = 0; k < 4; ++k) ad.w[k] = (v6 || k == 0) ? wg::allowed_be32(r.src_ip + 4 * k) : 0u;
+    if (!wg::allowed_contains(img->view, v6, ad, value[i])) r.kind = WG_TUNN_SKIPPED;
+  }
+  return rc;
 }
 
 int wg_tunn_decrypt_batch(wg_tunn *t, uint32_t n, const uint8_t *const *datagram,

@@ -259,6 +259,31 @@ class GpuContext:
         check(self._lib.wg_gpu_route_batch(self._h, _ptr(descs), n, _ptr(src), _stream(stream)),
               "wg_gpu_route_batch")
 
+    # --- AllowedIPs on the device (neptun_amd/allowed.py is the host table) ---
+    def allowed_set(self, table) -> None:
+        """Mirror an AllowedIps table's current image into HBM (None removes it; with no
+        image every lookup gives WG_ALLOWED_NONE / not allowed)."""
+        check(self._lib.wg_gpu_allowed_set(self._h, table._h if table is not None else None),
+              "wg_gpu_allowed_set", self._lib)
+
+    def allowed_route_batch(self, descs, n: int, src, value_out=None, set_key_slot: bool = True,
+                            stream=None) -> None:
+        """value_out[i] (device uint32, optional) and, if set_key_slot, descs[i].key_slot =
+        find(destination address of the plaintext IP packet at src + src_off)."""
+        check(self._lib.wg_gpu_allowed_route_batch(self._h, _ptr(descs), n, _ptr(src), _ptr(value_out),
+                                                   1 if set_key_slot else 0, _stream(stream)),
+              "wg_gpu_allowed_route_batch", self._lib)
+
+    def allowed_filter_batch(self, descs, n: int, dst, status, allowed_out, expect=None,
+                             slot_shift: int = 0, stream=None) -> None:
+        """After an open: allowed_out[i] (device uint8) = 1 if packet i opened and its
+        plaintext's source address lies in a network owned by expect[i] (device uint32;
+        None: descs[i].key_slot >> slot_shift), else 0."""
+        check(self._lib.wg_gpu_allowed_filter_batch(self._h, _ptr(descs), n, _ptr(dst), _ptr(status),
+                                                    _ptr(expect), slot_shift, _ptr(allowed_out),
+                                                    _stream(stream)),
+              "wg_gpu_allowed_filter_batch", self._lib)
+
     def seal_batch_ordered(self, descs, order, n: int, src, dst, status, stream=None) -> None:
         check(self._lib.wg_gpu_seal_batch_ordered(self._h, _ptr(descs), _ptr(order), n, _ptr(src),
                                                   _ptr(dst), _ptr(status), _stream(stream)),

@@ -16,7 +16,7 @@ import numpy as np
 from ._native import check, load
 from .gpu import GpuContext
 
-DONE, ERR, WRITE_TO_NETWORK, WRITE_TO_TUNNEL, NOT_DATA = 0, 1, 2, 3, 4
+DONE, ERR, WRITE_TO_NETWORK, WRITE_TO_TUNNEL, NOT_DATA, SKIPPED = 0, 1, 2, 3, 4, 5
 N_SESSIONS = 8
 
 
@@ -81,6 +81,9 @@ def _bind(L):
     L.wg_tunn_engine.restype = vp
     for fn in (L.wg_tunn_encapsulate_multi, L.wg_tunn_decapsulate_multi):
         fn.argtypes = [vp, u32, vp, vp, vp, vp, vp, c.POINTER(TunnResult)]
+    L.wg_tunn_encapsulate_routed.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, c.POINTER(TunnResult), vp]
+    L.wg_tunn_decapsulate_multi_allowed.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp,
+                                                    c.POINTER(TunnResult)]
     L._tunn_bound = True
     return L
 
@@ -192,6 +195,87 @@ class Engine:
     def decapsulate_multi_ptrs(self, tunn_ptrs, src_ptrs, src_lens, dst_ptrs, dst_caps):
         return self._multi_ptrs(self._lib.wg_tunn_decapsulate_multi, "wg_tunn_decapsulate_multi", tunn_ptrs,
                                 src_ptrs, src_lens, dst_ptrs, dst_caps)
+
+
+    def encapsulate_routed(self, table, peers, srcs, dsts):
+        """packet i through peers[table.find(destination of srcs[i])]
+        (wg_tunn_encapsulate_routed); -> (results, values).  Packets without a route
+        come back SKIPPED and consume nothing."""
+        return _routed(self._lib, self._h, table, peers, srcs, dsts)
+
+    def decapsulate_multi_allowed(self, table, peers, values, datagrams, dsts):
+        """datagram i through peers[values[i]], then WRITE_TO_TUNNEL results whose source
+        is not in a network owned by values[i] become SKIPPED
+        (wg_tunn_decapsulate_multi_allowed)."""
+        return _decap_allowed(self._lib, self._h, table, peers, values, datagrams, dsts)
+
+    def encapsulate_routed_ptrs(self, table, peers, src_ptrs, src_lens, dst_ptrs, dst_caps):
+        """over raw addresses (numpy uint64 / uint32 arrays); -> (results, values)"""
+        return _routed_ptrs(self._lib, self._h, table, peers, src_ptrs, src_lens, dst_ptrs, dst_caps)
+
+    def decapsulate_multi_allowed_ptrs(self, table, peers, values, src_ptrs, src_lens, dst_ptrs, dst_caps):
+        return _decap_allowed_ptrs(self._lib, self._h, table, peers, values, src_ptrs, src_lens, dst_ptrs,
+                                   dst_caps)
+
+
+def _peer_array(peers):
+    return (ctypes.c_void_p * max(len(peers), 1))(*[p._h.value if p is not None else None for p in peers])
+
+
+def _routed_ptrs(L, eng, table, peers, src_ptrs, src_lens, dst_ptrs, dst_caps):
+    n = len(src_ptrs)
+    res = (TunnResult * n)()
+    val = np.zeros(n, np.uint32)
+    vp = ctypes.c_void_p
+    check(L.wg_tunn_encapsulate_routed(eng, table._h, _peer_array(peers), len(peers), n,
+                                       vp(src_ptrs.ctypes.data), vp(src_lens.ctypes.data),
+                                       vp(dst_ptrs.ctypes.data), vp(dst_caps.ctypes.data), res,
+                                       vp(val.ctypes.data)), "wg_tunn_encapsulate_routed")
+    return _results(res), val
+
+
+def _routed(L, eng, table, peers, srcs, dsts):
+    n = len(srcs)
+    keep, sp, sl, dp, dc = _packet_arrays(srcs, dsts)
+    res = (TunnResult * n)()
+    val = (ctypes.c_uint32 * max(n, 1))()
+    check(L.wg_tunn_encapsulate_routed(eng, table._h, _peer_array(peers), len(peers), n, sp, sl, dp, dc, res,
+                                       val), "wg_tunn_encapsulate_routed")
+    return _results(res), np.array(val[:n], np.uint32)
+
+
+def _decap_allowed_ptrs(L, eng, table, peers, values, src_ptrs, src_lens, dst_ptrs, dst_caps):
+    n = len(src_ptrs)
+    res = (TunnResult * n)()
+    val = np.ascontiguousarray(values, np.uint32)
+    vp = ctypes.c_void_p
+    check(L.wg_tunn_decapsulate_multi_allowed(eng, table._h, _peer_array(peers), len(peers), n,
+                                              vp(val.ctypes.data), vp(src_ptrs.ctypes.data),
+                                              vp(src_lens.ctypes.data), vp(dst_ptrs.ctypes.data),
+                                              vp(dst_caps.ctypes.data), res),
+          "wg_tunn_decapsulate_multi_allowed")
+    return _results(res)
+
+
+def _decap_allowed(L, eng, table, peers, values, datagrams, dsts):
+    n = len(datagrams)
+    keep, sp, sl, dp, dc = _packet_arrays(datagrams, dsts)
+    res = (TunnResult * n)()
+    val = np.ascontiguousarray(values, np.uint32)
+    check(L.wg_tunn_decapsulate_multi_allowed(eng, table._h, _peer_array(peers), len(peers), n,
+                                              ctypes.c_void_p(val.ctypes.data), sp, sl, dp, dc, res),
+          "wg_tunn_decapsulate_multi_allowed")
+    return _results(res)
+
+
+def encapsulate_routed(table, peers, srcs, dsts):
+    """wg_tunn_encapsulate_routed with no engine: the peers on any engines."""
+    return _routed(_bind(table._lib), None, table, peers, srcs, dsts)
+
+
+def decapsulate_multi_allowed(table, peers, values, datagrams, dsts):
+    """wg_tunn_decapsulate_multi_allowed with no engine."""
+    return _decap_allowed(_bind(table._lib), None, table, peers, values, datagrams, dsts)
 
 
 def _multi_across(name, tunns, blobs, dsts):
